@@ -12,7 +12,16 @@ RCCL when N > 1 (torch.distributed's nccl backend; --engine-comm: the
 engine's own communicator through the C ABI, crdt_comm_init +
 crdt_context_allreduce_async, the form a Go caller binds).
 
-The same JSON line carries one "legs" entry per other BASELINE config, each
+A plain run does only what the headline figure needs: it generates the inputs,
+captures the step into a HIP graph, warms up, times the K steps once and prints
+the JSON line (metric, value, unit, ms_per_step, the headline's roofline from
+the timed launches).  --dump-outputs DIR then also writes what the last timed
+step computed (dump_outputs).  Everything else runs only with --full: the box
+bandwidth probes, the bitwise graph-replay check, two more timed repeats of the
+headline, the legs below, the ingest-sort and boundary-cost legs and the CPU
+baselines.
+
+With --full the same JSON line carries one "legs" entry per other BASELINE config, each
 timed the same way (warmup, barrier + synchronize, K steps, max over ranks),
 with its own roofline, graph-replay check and CPU baseline:
   config3: 10 ordered AWSetDelta sources folded into each of 1,048,576 docs (R = 16)
@@ -28,7 +37,8 @@ cpu_baseline: the hash-map C++ restatement of the reference merge
 sorted-array C oracle beside it; the CPU baselines run after every GPU timing
 (their samples are copied to the host as each config finishes).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--legs 3,4,5|none]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR]
+  python bench.py --full [--legs 3,4,5|none] [--repeats N] [--no-cpu-baseline] [--no-box-probe] ...
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 """
 
@@ -269,6 +279,9 @@ class Config2:
     def outputs(self):
         return _outs(self.oab, self.oba)
 
+    def results(self):
+        return {"a_from_b": self.oab, "b_from_a": self.oba}
+
     def post(self, s):
         """Per-GPU causal-context summary of the outputs; returns the R-vector.
         Both merges of a pair end with the same clock, dstVV max srcVV
@@ -442,6 +455,9 @@ class Config3:
     def outputs(self):
         return _outs(self.out)
 
+    def results(self):
+        return {"folded": self.out}
+
     def post(self, s):
         self.eng.causal_context_async(self.out.vv, self.n, self.R, self.ctx, stream=s)
         return self.ctx
@@ -597,9 +613,77 @@ def _box_fields(roof, box):
         roof["box_xcds"] = ident.get("xcds")
 
 
-def run_config(config, n, args, ctx, steps, warmup, repeats, cpu, box=None):
+def _split_u64(t):
+    """A device tensor of u64 words (held as int64) or u32 words (int32) as exact
+    float64: u64 -> [n, 2] (high, low 32-bit halves), u32 -> [n]."""
+    import numpy as np
+
+    a = t.cpu().numpy()
+    if a.dtype == np.int32:
+        return a.view(np.uint32).astype(np.float64)
+    a = a.view(np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take, all files together
+
+
+def dump_outputs(W, context, out_dir, seed):
+    """What the timed step computed, as a caller of the hot path receives it, written
+    as float64 .npy files under out_dir (u64 words as [n, 2] high / low 32-bit halves,
+    so every value is exact).  The outputs of a full-size batch are gigabytes, so the
+    files hold a fixed sample: the documents are taken in the order of a permutation
+    seeded by `seed` for as long as their live entries fit the byte budget.  Per result
+    buffer NAME of the workload (config 2/4: a_from_b, b_from_a; config 3/5: folded):
+      NAME_offsets, NAME_counts  slot start and live entries of each sampled document
+      NAME_vv                    its version vector, [docs * R, 2]
+      NAME_keys, NAME_actors, NAME_counters  its live entries, document after document
+    plus sample_docs (the sampled document numbers) and causal_context (the step's
+    all-reduced R-word summary).  Same arguments, same inputs, same sample: two builds
+    of the library can be compared file by file."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    res = W.results()
+    n, R = W.n, W.R
+    dev = next(iter(res.values())).vv.device
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    perm = np.random.default_rng(seed).permutation(n)
+    # live entries per document over every result buffer: 40 B each as float64 (keys and
+    # counters 16 B, actors 8 B); 16 B of bounds, 16 B * R of clock and 8 B of index per buffer
+    live = sum(o.counts.cpu().numpy().view(np.uint32).astype(np.int64) for o in res.values())
+    per_doc = live[perm] * 40 + len(res) * (16 + 16 * R) + 8
+    take = int(np.searchsorted(np.cumsum(per_doc), DUMP_BUDGET_BYTES, side="right"))
+    docs = np.sort(perm[:take])
+    d_docs = torch.from_numpy(docs).to(dev)
+    files = {"sample_docs": docs.astype(np.float64), "causal_context": _split_u64(context)}
+    for name, o in res.items():
+        off = o.offsets[:n][d_docs]
+        cnt = o.counts[d_docs]
+        st, c = off.cpu().numpy().view(np.uint32).astype(np.int64), cnt.cpu().numpy().view(np.uint32).astype(np.int64)
+        idx = np.repeat(st, c) + (np.arange(int(c.sum())) - np.repeat(np.cumsum(c) - c, c))
+        d_idx = torch.from_numpy(idx).to(dev)
+        vv_idx = (d_docs.view(-1, 1) * R + torch.arange(R, device=dev).view(1, R)).view(-1)
+        files[name + "_offsets"] = _split_u64(off)
+        files[name + "_counts"] = _split_u64(cnt)
+        files[name + "_vv"] = _split_u64(o.vv[vv_idx])
+        files[name + "_keys"] = _split_u64(o.keys[d_idx])
+        files[name + "_actors"] = _split_u64(o.actors[d_idx])
+        files[name + "_counters"] = _split_u64(o.counters[d_idx])
+    total = sum(a.nbytes for a in files.values())
+    assert total <= 64 << 20, total
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": len(files), "bytes": total, "docs": int(take)}
+
+
+def run_config(config, n, args, ctx, steps, warmup, repeats, cpu, box=None, check_replay=True, dump_dir=None):
     """Build one workload, time it, and return its result dict (the bench line's
-    fields).  Inputs are generated on the device before any timing."""
+    fields).  Inputs are generated on the device before any timing.  check_replay:
+    compare the captured graph's output bitwise with an eager launch before timing.
+    dump_dir: write the last timed step's outputs there (dump_outputs)."""
     import numpy as np
     import torch
 
@@ -618,15 +702,16 @@ def run_config(config, n, args, ctx, steps, warmup, repeats, cpu, box=None):
 
     # The dominant launch is captured once into a HIP graph and replayed each
     # step: one host call per step instead of the ABI calls of every kernel.
-    # Before timing, the replayed output is compared bitwise with an eager launch.
+    # With check_replay, the replayed output is compared bitwise with an eager launch before timing.
     graph, post_graph, replay_check, graph_error, graph_ctx = None, None, None, None, None
     if not args.no_graph:
         try:
-            for t in W.outputs():  # poison, so a replay that writes nothing cannot pass
-                t.fill_(-1)
+            if check_replay:
+                for t in W.outputs():  # poison, so a replay that writes nothing cannot pass
+                    t.fill_(-1)
             W.hot(stream)  # eager launch; also warms the workspaces (no allocation during capture)
             torch.cuda.synchronize()
-            eager = [t.clone() for t in W.outputs()]
+            eager = [t.clone() for t in W.outputs()] if check_replay else None
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 W.hot(torch.cuda.current_stream())
@@ -634,11 +719,12 @@ def run_config(config, n, args, ctx, steps, warmup, repeats, cpu, box=None):
             with torch.cuda.graph(gp):
                 graph_ctx = W.post(torch.cuda.current_stream())
             torch.cuda.synchronize()
-            for t in W.outputs():
-                t.fill_(-1)
-            g.replay()
-            torch.cuda.synchronize()
-            replay_check = all(bool(torch.equal(a, b)) for a, b in zip(eager, W.outputs()))
+            if check_replay:
+                for t in W.outputs():
+                    t.fill_(-1)
+                g.replay()
+                torch.cuda.synchronize()
+                replay_check = all(bool(torch.equal(a, b)) for a, b in zip(eager, W.outputs()))
             del eager
             graph, post_graph = g, gp
         except Exception as e:  # capture refused: report it and launch eagerly
@@ -725,6 +811,8 @@ def run_config(config, n, args, ctx, steps, warmup, repeats, cpu, box=None):
     _box_fields(res["roofline"], box)
     if per_merge_bytes != bytes_launch:
         res["roofline"]["survey_8d_per_merge_bytes"] = per_merge_bytes
+    if dump_dir and rank == 0:
+        res["dump_outputs"] = dump_outputs(W, g, dump_dir, args.seed)
     if graph_error:
         res["graph_error"] = graph_error
     if extra:
@@ -828,12 +916,20 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5], help="the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line can carry: box bandwidth probes, "
+                         "graph-replay check, timed repeats, the config legs, ingest sort, boundary cost and CPU "
+                         "baselines (each can be switched off by its own option below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a fixed, seeded sample of the last step's outputs to "
+                         "DIR/<name>.npy (float64, exact; see dump_outputs)")
     ap.add_argument("--legs", default=None,
-                    help="comma-separated configs timed after the headline (default with --config 2: 3,4,5; "
+                    help="--full: comma-separated configs timed after the headline (default with --config 2: 3,4,5; "
                          "otherwise none); 'none' for the headline only")
     ap.add_argument("--leg-steps", type=int, default=50)
     ap.add_argument("--leg-warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3, help="timed runs of the headline (the first is the value)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed runs of the headline (the first is the value; default 3 with --full, otherwise 1)")
     ap.add_argument("--docs", type=int, default=None, help="documents per GPU for the headline")
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--cpu-budget", type=float, default=3.0, help="seconds per CPU baseline variant")
@@ -851,6 +947,10 @@ def main():
                          "(crdt_comm_init + crdt_context_allreduce_async) instead of torch.distributed's")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
     args = ap.parse_args()
+    full = args.full
+    if not full and args.legs not in (None, "none"):
+        ap.error("--legs needs --full")
+    repeats = args.repeats if args.repeats is not None else (3 if full else 1)
 
     import torch
 
@@ -899,16 +999,18 @@ def main():
             collective = "torch.distributed %s all-reduce of host copies (rehearsal)" % backend
     ctx = (eng, dev, stream, dist, world, rank, engine_comm)
 
-    if args.legs is None:
-        legs = [3, 4, 5] if args.config == 2 else []
-    elif args.legs == "none":
+    if not full or args.legs == "none":
         legs = []
+    elif args.legs is None:
+        legs = [3, 4, 5] if args.config == 2 else []
     else:
         legs = [int(x) for x in args.legs.split(",") if x and int(x) != args.config]
+    cpu = full and not args.no_cpu_baseline
 
-    box = None if args.no_box_probe else box_probe(eng, dev)
+    box = box_probe(eng, dev) if full and not args.no_box_probe else None
     n = args.docs or DEFAULT_DOCS[args.config]
-    head = run_config(args.config, n, args, ctx, args.steps, args.warmup, args.repeats, not args.no_cpu_baseline, box)
+    head = run_config(args.config, n, args, ctx, args.steps, args.warmup, repeats, cpu, box, check_replay=full,
+                      dump_dir=args.dump_outputs)
     result = {
         "metric": head.pop("metric"),
         "value": head.pop("value"),
@@ -938,10 +1040,10 @@ def main():
         result["legs"] = {}
         for c in legs:
             result["legs"]["config%d" % c] = run_config(c, DEFAULT_DOCS[c], args, ctx, args.leg_steps,
-                                                        args.leg_warmup, 1, not args.no_cpu_baseline, box)
-    if rank == 0 and world == 1 and not args.no_sort:
+                                                        args.leg_warmup, 1, cpu, box)
+    if full and rank == 0 and world == 1 and not args.no_sort:
         result["ingest_sort"] = ingest_sort_leg(eng, dev, stream, DEFAULT_DOCS[2], args.seed)
-    if rank == 0 and world == 1 and not args.no_boundary:
+    if full and rank == 0 and world == 1 and not args.no_boundary:
         result["boundary"] = boundary_cost(args.boundary_docs)
         if not args.no_sort:
             bs = ingest_sort_leg(eng, dev, stream, args.boundary_docs, args.seed)

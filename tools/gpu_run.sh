@@ -34,7 +34,8 @@ set -u
 cd "$(dirname "$0")/.."
 source tools/gpu_step.sh
 TAG=${TAG:-r04}
-BENCH_ARGS=${BENCH_ARGS:-}
+# bench, prof and configs record the whole line (legs, probes, CPU baselines): bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for r in "$@"; do
   case $r in
     tests)
