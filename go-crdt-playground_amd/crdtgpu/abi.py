@@ -30,6 +30,9 @@ CRDT_COMM_ID_BYTES = 128
 CRDT_MAX_R = 64
 CRDT_FOLD_AWSET = 0
 CRDT_FOLD_DELTA = 1
+CRDT_DELTA_NONE = 0
+CRDT_DELTA_DELTA = 1
+CRDT_DELTA_FULL = 2
 CRDT_OP_ADD = 0
 CRDT_OP_DEL = 1
 CRDT_OP_DELTA_DEL = 2
@@ -65,6 +68,15 @@ class CSrcBatch(ctypes.Structure):
         ("doc_srcs", _vp), ("src_actor", _vp), ("vv", _vp), ("entry_off", _vp),
         ("keys", _vp), ("actors", _vp), ("counters", _vp),
         ("tomb_off", _vp), ("tkeys", _vp), ("tactors", _vp), ("tcounters", _vp),
+    ]
+
+
+class CDeltaOut(ctypes.Structure):
+    _fields_ = [
+        ("doc_srcs", _vp), ("src_actor", _vp), ("vv", _vp), ("entry_off", _vp),
+        ("keys", _vp), ("actors", _vp), ("counters", _vp),
+        ("tomb_off", _vp), ("tkeys", _vp), ("tactors", _vp), ("tcounters", _vp),
+        ("kind", _vp),
     ]
 
 
@@ -149,6 +161,8 @@ def signatures():
                                                      P(CAWSetOut), _vp]),
         "crdt_awset_exchange_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), P(CAWSetOut), P(CAWSetOut)]),
         "crdt_awset_fold_async": (ctypes.c_int, [_vp, ctypes.c_int, P(CAWSetBatch), P(CSrcBatch), P(CAWSetOut), _vp]),
+        "crdt_awset_delta_extract_async": (ctypes.c_int, [_vp, P(CSrcBatch), _vp, P(CDeltaOut), _vp]),
+        "crdt_awset_delta_extract_batch": (ctypes.c_int, [_vp, P(CSrcBatch), _vp, P(CDeltaOut)]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import CAWSetBatch, CAWSetOut, COpBatch, CSrcBatch, CTombBatch, CTombOut
+from .abi import CAWSetBatch, CAWSetOut, CDeltaOut, COpBatch, CSrcBatch, CTombBatch, CTombOut
 
 U32, U64 = np.uint32, np.uint64
 
@@ -199,6 +199,12 @@ class SrcBatch:
         return CSrcBatch(self.n_docs, self.R, ptr(self.doc_srcs), ptr(self.src_actor), ptr(self.vv),
                          ptr(self.entry_off), ptr(self.keys), ptr(self.actors), ptr(self.counters),
                          ptr(self.tomb_off), ptr(self.tkeys), ptr(self.tactors), ptr(self.tcounters))
+
+    def c_delta_out(self, kind=None) -> CDeltaOut:
+        """These arrays as the message a delta extraction writes (crdt_delta_out)."""
+        return CDeltaOut(ptr(self.doc_srcs), ptr(self.src_actor), ptr(self.vv), ptr(self.entry_off), ptr(self.keys),
+                         ptr(self.actors), ptr(self.counters), ptr(self.tomb_off), ptr(self.tkeys),
+                         ptr(self.tactors), ptr(self.tcounters), ptr(kind))
 
     _FIELDS = (("doc_srcs", U32), ("src_actor", U32), ("vv", U64), ("entry_off", U32), ("keys", U64),
                ("actors", U32), ("counters", U64), ("tomb_off", U32), ("tkeys", U64), ("tactors", U32),

@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import AWSetBatch, OpBatch, OutBuffers, SrcBatch, TombBatch, TombBuffers, ptr
+from .batch import AWSetBatch, OpBatch, OutBuffers, SrcBatch, SrcBuffers, TombBatch, TombBuffers, _np, ptr
 
 
 def _c(x):
@@ -90,6 +90,14 @@ class Engine:
         d, s, o = _c(dst), _c(srcs), _c(out)
         check(self._lib.crdt_awset_fold_async(self._ctx, int(mode), ctypes.byref(d), ctypes.byref(s),
                                               ctypes.byref(o), _stream(stream)), "crdt_awset_fold_async")
+
+    def delta_extract_async(self, srcs: SrcBatch, peer_vv, out: SrcBuffers, kind=None, stream=None):
+        """Send side of anti-entropy: per doc, what a peer that has reached clock
+        peer_vv[d*R..] still needs of each AWSetDelta source, packed into `out`
+        (crdt_awset_delta_extract_async); kind: u8 per source, CRDT_DELTA_*."""
+        s, o = _c(srcs), out.c_delta_out(kind)
+        check(self._lib.crdt_awset_delta_extract_async(self._ctx, ctypes.byref(s), ptr(peer_vv), ctypes.byref(o),
+                                                       _stream(stream)), "crdt_awset_delta_extract_async")
 
     def vv_max_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_max_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
@@ -203,6 +211,27 @@ class Engine:
                                                ctypes.byref(co), ctypes.byref(cout),
                                                ctypes.byref(cto) if cto else None), "crdt_awset_apply_batch")
         return out, tout
+
+    def delta_extract(self, srcs: SrcBatch, peer_vv):
+        """Host buffers: (the message as a SrcBatch trimmed to its packed sizes,
+        kind per source as a numpy uint8 array)."""
+        import numpy as np
+
+        srcs = srcs.numpy()
+        ns = int(srcs.doc_srcs[-1])
+        ne = int(srcs.entry_off[ns])
+        nt = int(srcs.tomb_off[ns]) if srcs.tomb_off is not None else 0
+        peer = _np(peer_vv if hasattr(peer_vv, "dtype") else np.asarray(peer_vv, dtype=np.uint64), np.uint64)
+        out = SrcBuffers(srcs.R, srcs.n_docs, ns, ne, nt)
+        kind = np.zeros(max(ns, 1), dtype=np.uint8)
+        s, o = srcs.c(), out.c_delta_out(kind)
+        check(self._lib.crdt_awset_delta_extract_batch(self._ctx, ctypes.byref(s), ptr(peer), ctypes.byref(o)),
+              "crdt_awset_delta_extract_batch")
+        te, tt = int(out.entry_off[ns]), int(out.tomb_off[ns])
+        msg = SrcBatch(srcs.R, out.doc_srcs, out.src_actor, out.vv[: ns * srcs.R], out.entry_off, out.keys[:te],
+                       out.actors[:te], out.counters[:te], out.tomb_off, out.tkeys[:tt], out.tactors[:tt],
+                       out.tcounters[:tt])
+        return msg, kind[:ns]
 
     def fold(self, mode: int, dst: AWSetBatch, srcs: SrcBatch, pinned: bool = False) -> OutBuffers:
         dst, srcs = dst.numpy(), srcs.numpy()

@@ -40,6 +40,8 @@ hipError_t launch_sort(const BatchView& in, uint32_t n_slots, const OutView& out
                        uint32_t* ends, uint32_t* idx, uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_apply(const BatchView& st, const TombView& tb, const ApplyOps& ops, const OutView& out,
                         const TombOut& tout, bool has_tout, const Work& wk, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_extract(const SrcView& sv, const uint64_t* peer, const DeltaOutView& out, uint32_t* gcnt_e,
+                          uint32_t* gcnt_t, const Work& wk, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -629,6 +631,31 @@ int crdt_awset_fold_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, 
                 slots};
     rc = hip_err(launch_fold(mode, view(dst), view(srcs), view(out), scr, make_work(ctx), block_grid(ctx),
                              ctx->fold_lean_first, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// The group counts of the extraction (extract.hip) live in the worklist and
+// defer buffers: one word per group of 64 / R documents each, at most n_docs,
+// which is what crdt_ctx_reserve(max_docs, ..) sizes them for.
+int crdt_awset_delta_extract_async(crdt_ctx* ctx, const crdt_src_batch* srcs, const uint64_t* peer_vv,
+                                   const crdt_delta_out* out, void* stream) {
+    if (!ctx || !src_ptrs_ok(srcs) || !out || (srcs->n_docs && !peer_vv)) return CRDT_E_INVALID;
+    if (!out->doc_srcs || !out->src_actor || !out->vv || !out->entry_off || !out->keys || !out->actors ||
+        !out->counters)
+        return CRDT_E_INVALID;
+    if (srcs->tomb_off && (!out->tomb_off || !out->tkeys || !out->tactors || !out->tcounters)) return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(srcs->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(srcs->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    const DeltaOutView ov{out->doc_srcs, out->src_actor, out->vv,    out->entry_off, out->keys,      out->actors,
+                          out->counters, out->tomb_off,  out->tkeys, out->tactors,   out->tcounters, out->kind};
+    rc = hip_err(launch_extract(view(srcs), peer_vv, ov, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(),
+                                make_work(ctx), (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 
@@ -1401,6 +1428,86 @@ int crdt_awset_fold_batch(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, 
     bool copied = false;
     if (rc == CRDT_OK) rc = fetch_outputs(ctx, st, 1, hs, &dout, keys, dst->n_docs, dst->R, total, &copied);
     const int sync = finish(ctx, copied);
+    return rc != CRDT_OK ? rc : sync;
+}
+
+// Two syncs: the packed totals come back first (8 bytes), then exactly the
+// live prefix of each entry and tombstone array.
+int crdt_awset_delta_extract_batch(crdt_ctx* ctx, const crdt_src_batch* srcs, const uint64_t* peer_vv,
+                                   const crdt_delta_out* out) {
+    if (!ctx || !out) return CRDT_E_INVALID;
+    int rc = validate_src_batch(srcs, false);
+    if (rc != CRDT_OK) return rc;
+    if (srcs->n_docs && !peer_vv) return CRDT_E_INVALID;
+    if (!out->doc_srcs || !out->src_actor || !out->vv || !out->entry_off || !out->keys || !out->actors ||
+        !out->counters)
+        return CRDT_E_INVALID;
+    if (srcs->tomb_off && (!out->tomb_off || !out->tkeys || !out->tactors || !out->tcounters)) return CRDT_E_INVALID;
+    const uint32_t n = srcs->n_docs, R = srcs->R;
+    const uint32_t ns = srcs->doc_srcs[n];
+    const size_t ne = srcs->entry_off[ns];
+    const size_t nt = srcs->tomb_off ? srcs->tomb_off[ns] : 0;
+    if (srcs->doc_srcs[0] != 0 || (ne && (!srcs->keys || !srcs->actors || !srcs->counters))) return CRDT_E_INVALID;
+    if ((rc = set_device(ctx)) != CRDT_OK) return rc;
+    Stager st{ctx};
+    crdt_src_batch ds = *srcs;
+    const uint64_t* dpeer = nullptr;
+    st.plan([&] {
+        ds.doc_srcs = st.put(srcs->doc_srcs, (size_t)n + 1);
+        ds.src_actor = st.put(srcs->src_actor, ns);
+        ds.vv = st.put(srcs->vv, (size_t)ns * R);
+        ds.entry_off = st.put(srcs->entry_off, (size_t)ns + 1);
+        ds.keys = st.put(srcs->keys, ne);
+        ds.actors = st.put(srcs->actors, ne);
+        ds.counters = st.put(srcs->counters, ne);
+        if (srcs->tomb_off) {
+            ds.tomb_off = st.put(srcs->tomb_off, (size_t)ns + 1);
+            ds.tkeys = st.put(srcs->tkeys, nt);
+            ds.tactors = st.put(srcs->tactors, nt);
+            ds.tcounters = st.put(srcs->tcounters, nt);
+        }
+        dpeer = st.put(peer_vv, (size_t)n * R);
+    });
+    crdt_delta_out dout{};
+    dout.doc_srcs = st.room<uint32_t>((size_t)n + 1);
+    dout.src_actor = st.room<uint32_t>(ns);
+    dout.vv = st.room<uint64_t>((size_t)ns * R);
+    dout.entry_off = st.room<uint32_t>((size_t)ns + 1);
+    dout.keys = st.room<uint64_t>(ne);
+    dout.actors = st.room<uint32_t>(ne);
+    dout.counters = st.room<uint64_t>(ne);
+    dout.tomb_off = st.room<uint32_t>((size_t)ns + 1);
+    dout.tkeys = st.room<uint64_t>(nt);
+    dout.tactors = st.room<uint32_t>(nt);
+    dout.tcounters = st.room<uint64_t>(nt);
+    dout.kind = st.room<uint8_t>(ns);
+    st.flush();  // the inputs' span, if they lie in one crdt_host_alloc block
+    if (st.rc != CRDT_OK) return st.rc;
+    rc = srcs->tomb_off ? check_order(ctx, {{ds.entry_off, nullptr, ns, ds.keys}, {ds.tomb_off, nullptr, ns, ds.tkeys}})
+                        : check_order(ctx, {{ds.entry_off, nullptr, ns, ds.keys}});
+    if (rc == CRDT_OK)
+        rc = gated(ctx, [&] { return crdt_awset_delta_extract_async(ctx, &ds, dpeer, &dout, ctx->stream); });
+    uint32_t tot_e = 0, tot_t = 0;
+    if (rc == CRDT_OK) rc = get(&tot_e, dout.entry_off + ns, 1, ctx->stream);
+    if (rc == CRDT_OK) rc = get(&tot_t, dout.tomb_off + ns, 1, ctx->stream);
+    int sync = crdt_ctx_sync(ctx, ctx->stream);  // (an order violation ends the call here)
+    if (rc != CRDT_OK || sync != CRDT_OK) return rc != CRDT_OK ? rc : sync;
+    if (tot_e > ne || tot_t > nt) return CRDT_E_CAPACITY;  // (the kept are a subset of the input: never)
+    rc = get(out->doc_srcs, dout.doc_srcs, (size_t)n + 1, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->src_actor, dout.src_actor, ns, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->vv, dout.vv, (size_t)ns * R, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->entry_off, dout.entry_off, (size_t)ns + 1, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->keys, dout.keys, tot_e, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->actors, dout.actors, tot_e, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->counters, dout.counters, tot_e, ctx->stream);
+    if (rc == CRDT_OK && out->tomb_off) rc = get(out->tomb_off, dout.tomb_off, (size_t)ns + 1, ctx->stream);
+    if (rc == CRDT_OK && srcs->tomb_off) {
+        rc = get(out->tkeys, dout.tkeys, tot_t, ctx->stream);
+        if (rc == CRDT_OK) rc = get(out->tactors, dout.tactors, tot_t, ctx->stream);
+        if (rc == CRDT_OK) rc = get(out->tcounters, dout.tcounters, tot_t, ctx->stream);
+    }
+    if (rc == CRDT_OK && out->kind) rc = get(out->kind, dout.kind, ns, ctx->stream);
+    sync = crdt_ctx_sync(ctx, ctx->stream);
     return rc != CRDT_OK ? rc : sync;
 }
 

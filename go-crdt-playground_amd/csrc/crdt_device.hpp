@@ -57,6 +57,22 @@ struct SrcView {
     const uint64_t* tcounters;
 };
 
+// The message a delta extraction writes (extract.hip; same fields as crdt_delta_out).
+struct DeltaOutView {
+    uint32_t* doc_srcs;
+    uint32_t* src_actor;
+    uint64_t* vv;
+    uint32_t* entry_off;
+    uint64_t* keys;
+    uint32_t* actors;
+    uint64_t* counters;
+    uint32_t* tomb_off;  // may be NULL when the input has no tombstones
+    uint64_t* tkeys;
+    uint32_t* tactors;
+    uint64_t* tcounters;
+    uint8_t* kind;  // may be NULL
+};
+
 // Scratch copy of the output slots (fold block path ping-pong), `slots` long.
 struct Scratch {
     uint64_t* keys;

@@ -14,6 +14,7 @@
 //	both directions      awset.go:103 twice          -> Engine.ExchangeBatch (one snapshot)
 //	ordered AWSet merges awset.go:103, in order      -> Engine.FoldBatch
 //	(*AWSetDelta).Merge  awset-delta_test.go:51-166  -> Engine.DeltaMerge / DeltaMergeBatch
+//	MakeDeltaMergeData   awset-delta_test.go:79-105  -> Engine.DeltaBatch (what to send a peer)
 //
 // AWSetDelta lives in a _test.go file of the reference, invisible to importers,
 // so this package defines it (with Del and Clone, awset-delta_test.go:9-49).
@@ -509,6 +510,111 @@ func (e *Engine) fold(delta bool, dsts []*crdt.AWSet, ds []docState, ss [][]docS
 		o.apply(i, R, widths[i], keys[i], dst)
 	}
 	return nil
+}
+
+// ---------------------------------------------------------------- delta extraction
+
+// Delta is what one source state has to send a peer: Kind is CRDT_DELTA_NONE
+// (nothing: skip it), CRDT_DELTA_DELTA or CRDT_DELTA_FULL (first contact), and
+// State holds the entries and tombstones to ship with the source's actor and
+// clock. The receiver merges State with DeltaMerge / DeltaMergeBatch.
+type Delta struct {
+	Kind  int
+	State *AWSetDelta
+}
+
+// DeltaBatch is the sending side of anti-entropy: for every i and every state
+// s of srcs[i], what a peer whose replica of document i has reached the clock
+// peers[i] still needs of s -- MakeDeltaMergeData(peers[i])
+// (awset-delta_test.go:79-105) or, at Counter(s.Actor) == 0, the whole state
+// (:53) -- in one call (crdt_awset_delta_extract_batch). For any peers[i] at or
+// below the receiver's real clock, merging the result equals merging the states.
+// Clocks shorter than the longest one of the batch count as padded with zeros.
+func (e *Engine) DeltaBatch(srcs [][]*AWSetDelta, peers []crdt.VersionVector) ([][]Delta, error) {
+	if len(srcs) != len(peers) {
+		return nil, fmt.Errorf("DeltaBatch: %d source lists, %d peer clocks", len(srcs), len(peers))
+	}
+	n := len(srcs)
+	res := make([][]Delta, n)
+	if n == 0 {
+		return res, nil
+	}
+	keys := make([]docKeys, n)
+	R, ns, nent, ntomb := 1, 0, 0, 0
+	for i, l := range srcs {
+		R = max(R, len(peers[i]))
+		var maps []map[string]crdt.Dot
+		for _, s := range l {
+			R = max(R, len(s.VersionVector))
+			maps = append(maps, s.Entries, s.Deleted)
+			nent += len(s.Entries)
+			ntomb += len(s.Deleted)
+		}
+		ns += len(l)
+		keys[i] = internDoc(maps...)
+	}
+	var a arena
+	defer a.free()
+	docSrcs, srcActor, svv, pvv := a.u32(n+1), a.u32(ns), a.u64(ns*R), a.u64(n*R)
+	eoff, ent, toff, tomb := a.u32(ns+1), a.entries(nent), a.u32(ns+1), a.entries(ntomb)
+	oDocSrcs, oActor, ovv := a.u32(n+1), a.u32(ns), a.u64(ns*R)
+	oeoff, oent, otoff, otomb := a.u32(ns+1), a.entries(nent), a.u32(ns+1), a.entries(ntomb)
+	kind := a.u32((ns + 3) / 4) // ns bytes
+	if a.err != nil {
+		return nil, a.err
+	}
+	q, at, tat := 0, 0, 0
+	for i, l := range srcs {
+		docSrcs[i] = uint32(q)
+		putVV(pvv[i*R:(i+1)*R], peers[i])
+		for _, s := range l {
+			srcActor[q] = uint32(s.Actor)
+			putVV(svv[q*R:(q+1)*R], s.VersionVector)
+			eoff[q], toff[q] = uint32(at), uint32(tat)
+			at = ent.put(at, s.Entries, keys[i])
+			tat = tomb.put(tat, s.Deleted, keys[i])
+			q++
+		}
+	}
+	docSrcs[n], eoff[ns], toff[ns] = uint32(ns), uint32(nent), uint32(ntomb)
+	cs := C.crdt_src_batch{n_docs: C.uint32_t(n), R: C.uint32_t(R), doc_srcs: p32(docSrcs),
+		src_actor: p32(srcActor), vv: p64(svv), entry_off: p32(eoff), keys: p64(ent.keys),
+		actors: p32(ent.actors), counters: p64(ent.counters), tomb_off: p32(toff), tkeys: p64(tomb.keys),
+		tactors: p32(tomb.actors), tcounters: p64(tomb.counters)}
+	dout := C.crdt_delta_out{doc_srcs: p32(oDocSrcs), src_actor: p32(oActor), vv: p64(ovv), entry_off: p32(oeoff),
+		keys: p64(oent.keys), actors: p32(oent.actors), counters: p64(oent.counters), tomb_off: p32(otoff),
+		tkeys: p64(otomb.keys), tactors: p32(otomb.actors), tcounters: p64(otomb.counters),
+		kind: (*C.uint8_t)(unsafe.Pointer(unsafe.SliceData(kind)))}
+	if rc := C.crdt_awset_delta_extract_batch(e.ctx, &cs, p64(pvv), &dout); rc != 0 {
+		return nil, errOf("crdt_awset_delta_extract_batch", rc)
+	}
+	kinds := unsafe.Slice((*uint8)(unsafe.Pointer(unsafe.SliceData(kind))), ns)
+	dots := func(es entries, lo, hi uint32, ks docKeys) map[string]crdt.Dot {
+		if lo == hi {
+			return nil
+		}
+		m := make(map[string]crdt.Dot, hi-lo)
+		for j := lo; j < hi; j++ {
+			m[ks[es.keys[j]]] = crdt.Dot{Actor: crdt.Actor(es.actors[j]), Counter: uint(es.counters[j])}
+		}
+		return m
+	}
+	q = 0
+	for i, l := range srcs {
+		res[i] = make([]Delta, len(l))
+		for j, s := range l {
+			st := &AWSetDelta{AWSet: crdt.AWSet{Actor: s.Actor}}
+			st.VersionVector = append(crdt.VersionVector(nil), s.VersionVector...)
+			st.Entries = dots(oent, oeoff[q], oeoff[q+1], keys[i])
+			if st.Entries == nil {
+				st.Entries = map[string]crdt.Dot{}
+			}
+			st.Deleted = dots(otomb, otoff[q], otoff[q+1], keys[i])
+			res[i][j] = Delta{Kind: int(kinds[q]), State: st}
+			q++
+		}
+	}
+	return res, nil
 }
 
 // foldWidth is len(dst.VersionVector) after the fold, replayed on the clocks

@@ -13,6 +13,10 @@
  *   crdt_awset_fold_async / crdt_awset_fold_batch, mode CRDT_FOLD_DELTA
  *       replace (*AWSetDelta).Merge with MakeDeltaMergeData, deltaMerge and
  *       the (no-op) gcDeleted                          awset-delta_test.go:51-166
+ *   crdt_awset_delta_extract_async / crdt_awset_delta_extract_batch
+ *       replace (*AWSetDelta).MakeDeltaMergeData and the path select of
+ *       (*AWSetDelta).Merge, run on the sending side against the clock the
+ *       peer is known to have reached          awset-delta_test.go:51-65,79-105
  *   crdt_vv_max_async
  *       replaces (*VersionVector).Merge                crdt-misc.go:43-55
  *   crdt_causal_context_async
@@ -215,6 +219,53 @@ int crdt_awset_exchange_async(crdt_ctx* ctx, const crdt_awset_batch* a, const cr
                               const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, void* stream);
 int crdt_awset_fold_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
                           const crdt_awset_out* out, void* stream);
+/* ---- delta extraction: the sending side of anti-entropy -------------------
+ * Given AWSetDelta source states and, per doc, the clock peer_vv[d*R..] the
+ * peer's replica of that doc is known to have reached (shared by the doc's
+ * sources), write the message to ship: a packed crdt_src_batch with the same
+ * n_docs, R and doc_srcs, src_actor and vv copied, and per source s of doc d,
+ * P = peer_vv[d*R..]:
+ *   tombstones = {(k,x) in Deleted : not (k in Entries and (e.actor != x.actor
+ *                or e.counter > x.counter))}   awset-delta_test.go:93-102; no
+ *                clock filter, the same for every kind
+ *   CRDT_DELTA_FULL   P.Counter(src_actor[s]) == 0 (first contact, :53): every
+ *                     entry; stays FULL when the state is empty
+ *   CRDT_DELTA_DELTA  otherwise: entries {(k,e) : !P.HasDot(e)}         :84-92
+ *   CRDT_DELTA_NONE   a DELTA with no entry and no tombstone to send (:60); the
+ *                     source keeps its (empty) slot in the message
+ * Entries and tombstones come out in key order; entry_off / tomb_off are the
+ * exclusive prefix sums over all sources (no slack), so entry_off[n_srcs] and
+ * tomb_off[n_srcs] are the totals shipped.  The message is a valid `srcs` of
+ * crdt_awset_fold_* in CRDT_FOLD_DELTA mode, and for any peer_vv <= the
+ * receiver's clock (elementwise; clocks only grow) folding it gives what
+ * folding the full states gives: the receiver prunes again, and a FULL source
+ * carries its tombstones in case the receiver has met that actor since.
+ * Counter(src_actor) at src_actor == R, and on the DELTA path HasDot of an
+ * entry dot with actor == R: CRDT_E_ACTOR_RANGE at sync (entry dots of a FULL
+ * source and tombstone dots are not tested).  Output capacity: the input's
+ * entry and tombstone slots.  srcs->tomb_off == NULL: no tombstones; out may
+ * then pass NULL tombstone arrays, and a tomb_off it does pass is zeroed.
+ * Workspace: two words per doc, sized by crdt_ctx_reserve(max_docs, ..). */
+#define CRDT_DELTA_NONE 0
+#define CRDT_DELTA_DELTA 1
+#define CRDT_DELTA_FULL 2
+typedef struct {            /* written; same layout as crdt_src_batch plus kind */
+    uint32_t* doc_srcs;     /* [n_docs+1]  */
+    uint32_t* src_actor;    /* [n_srcs]    */
+    uint64_t* vv;           /* [n_srcs*R]  */
+    uint32_t* entry_off;    /* [n_srcs+1]  */
+    uint64_t* keys;
+    uint32_t* actors;
+    uint64_t* counters;
+    uint32_t* tomb_off;     /* [n_srcs+1]  */
+    uint64_t* tkeys;
+    uint32_t* tactors;
+    uint64_t* tcounters;
+    uint8_t* kind;          /* [n_srcs] CRDT_DELTA_*, may be NULL */
+} crdt_delta_out;
+int crdt_awset_delta_extract_async(crdt_ctx* ctx, const crdt_src_batch* srcs, const uint64_t* peer_vv,
+                                   const crdt_delta_out* out, void* stream);
+
 /* dst[i] = max(dst[i], src[i]) for i < n (u64). */
 int crdt_vv_max_async(crdt_ctx* ctx, uint64_t* dst, const uint64_t* src, size_t n, void* stream);
 /* out[r] = max over d < n_docs of vv[d*R + r]  (the per-GPU causal-context summary). */
@@ -409,6 +460,11 @@ int crdt_awset_exchange_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const cr
                               const crdt_awset_out* out_ab, const crdt_awset_out* out_ba);
 int crdt_awset_fold_batch(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
                           const crdt_awset_out* out);
+/* Host arrays in and out: the slot layout is checked on the host, the key order
+ * of source entries and tombstones on the device (CRDT_E_UNSORTED), and only
+ * the packed live prefix of each output array is downloaded. */
+int crdt_awset_delta_extract_batch(crdt_ctx* ctx, const crdt_src_batch* srcs, const uint64_t* peer_vv,
+                                   const crdt_delta_out* out);
 
 /* ---- host-side validation of a packed batch (no GPU) -------------------- */
 int crdt_validate_batch(const crdt_awset_batch* b);
