@@ -9,6 +9,7 @@ from .abi import (CRDT_E_ACTOR_RANGE, CRDT_E_CAPACITY, CRDT_E_DUP_KEY, CRDT_E_HI
                   CRDT_OP_ADD, CRDT_OP_DEL, CRDT_OP_DELTA_DEL, CRDT_OP_DELTA_DEL_KEY,
                   CRDT_DELTA_NONE, CRDT_DELTA_DELTA, CRDT_DELTA_FULL,
                   CrdtError, LIB_PATH, header_functions, lib, strerror)
-from .batch import AWSetBatch, OpBatch, OutBuffers, SrcBatch, SrcBuffers, TombBatch, TombBuffers  # noqa: F401
+from .batch import (AWSetBatch, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers,  # noqa: F401
+                    TombBatch, TombBuffers)
 from .engine import (Engine, comm_unique_id, dump_batch, format_doc, global_context_allreduce,  # noqa: F401
                      load_batch, validate, validate_src)

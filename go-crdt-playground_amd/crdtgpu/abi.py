@@ -92,6 +92,14 @@ class CTombOut(ctypes.Structure):
     _fields_ = [("offsets", _vp), ("counts", _vp), ("keys", _vp), ("actors", _vp), ("counters", _vp)]
 
 
+class CQueryBatch(ctypes.Structure):
+    _fields_ = [("n_docs", _u32), ("n_queries", _u32), ("q_off", _vp), ("keys", _vp)]
+
+
+class CQueryOut(ctypes.Structure):
+    _fields_ = [("found", _vp), ("actors", _vp), ("counters", _vp)]
+
+
 class CrdtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -163,6 +171,9 @@ def signatures():
         "crdt_awset_fold_async": (ctypes.c_int, [_vp, ctypes.c_int, P(CAWSetBatch), P(CSrcBatch), P(CAWSetOut), _vp]),
         "crdt_awset_delta_extract_async": (ctypes.c_int, [_vp, P(CSrcBatch), _vp, P(CDeltaOut), _vp]),
         "crdt_awset_delta_extract_batch": (ctypes.c_int, [_vp, P(CSrcBatch), _vp, P(CDeltaOut)]),
+        "crdt_awset_has_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CQueryBatch), P(CQueryOut), _vp]),
+        "crdt_awset_has_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CQueryBatch), P(CQueryOut)]),
+        "crdt_tomb_has_async": (ctypes.c_int, [_vp, P(CTombBatch), _u32, P(CQueryBatch), P(CQueryOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

@@ -12,7 +12,8 @@ import ctypes
 
 import numpy as np
 
-from .abi import CAWSetBatch, CAWSetOut, CDeltaOut, COpBatch, CSrcBatch, CTombBatch, CTombOut
+from .abi import (CAWSetBatch, CAWSetOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CSrcBatch, CTombBatch,
+                  CTombOut)
 
 U32, U64 = np.uint32, np.uint64
 
@@ -360,6 +361,67 @@ class TombBuffers(TombBatch):
 
     def c_out(self) -> CTombOut:
         return CTombOut(ptr(self.offsets), ptr(self.counts), ptr(self.keys), ptr(self.actors), ptr(self.counters))
+
+
+class QueryBatch:
+    """Per doc a list of query keys (crdt_query_batch): doc d asks
+    keys[q_off[d]:q_off[d+1]], in any order, duplicates allowed."""
+
+    def __init__(self, q_off, keys, n_queries=None):
+        self.q_off, self.keys = q_off, keys
+        # host-known (crdt_query_batch.n_queries): read once here, never from a device q_off later
+        self.n_queries = int(_np(q_off, U32)[-1]) if n_queries is None else int(n_queries)
+
+    @property
+    def n_docs(self) -> int:
+        return int(self.q_off.shape[0]) - 1
+
+    def c(self) -> CQueryBatch:
+        return CQueryBatch(self.n_docs, self.n_queries, ptr(self.q_off), ptr(self.keys))
+
+    def numpy(self) -> "QueryBatch":
+        return QueryBatch(_np(self.q_off, U32), _np(self.keys, U64), self.n_queries)
+
+    def to(self, device) -> "QueryBatch":
+        return QueryBatch(_torch(self.q_off, device), _torch(self.keys, device), self.n_queries)
+
+    @staticmethod
+    def from_lists(per_doc_keys) -> "QueryBatch":
+        q_off = np.zeros(len(per_doc_keys) + 1, dtype=U32)
+        np.cumsum([len(x) for x in per_doc_keys], out=q_off[1:])
+        n = int(q_off[-1])
+        keys = np.zeros(max(n, 1), dtype=U64)
+        if n:
+            keys[:n] = np.concatenate([np.asarray(x, dtype=U64) for x in per_doc_keys if len(x)])
+        return QueryBatch(q_off, keys, n)
+
+
+class QueryBuffers:
+    """Outputs of a membership read (crdt_query_out), one per query: found (u8)
+    and, with dots, the entry's actor and counter.  numpy, or torch on `device`."""
+
+    def __init__(self, n_queries, device=None, dots=True):
+        self.n_queries = n = int(n_queries)
+        if device is None:
+            self.found = np.zeros(max(n, 1), np.uint8)
+            self.actors = np.zeros(max(n, 1), U32) if dots else None
+            self.counters = np.zeros(max(n, 1), U64) if dots else None
+        else:
+            import torch
+
+            e = lambda dt: torch.empty(max(n, 1), dtype=dt, device=device)  # noqa: E731
+            self.found = e(torch.uint8)
+            self.actors = e(torch.int32) if dots else None
+            self.counters = e(torch.int64) if dots else None
+
+    def c(self) -> CQueryOut:
+        return CQueryOut(ptr(self.found), ptr(self.actors), ptr(self.counters))
+
+    def numpy(self):
+        """(found, actors, counters) as numpy arrays of n_queries (dots absent: None)."""
+        n = self.n_queries
+        f = lambda a, dt: None if a is None else _np(a, dt)[:n]  # noqa: E731
+        return f(self.found, np.uint8), f(self.actors, U32), f(self.counters, U64)
 
 
 def c_ref(x):

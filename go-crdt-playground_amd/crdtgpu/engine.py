@@ -6,7 +6,8 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import AWSetBatch, OpBatch, OutBuffers, SrcBatch, SrcBuffers, TombBatch, TombBuffers, _np, ptr
+from .batch import (AWSetBatch, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
+                    TombBuffers, _np, ptr)
 
 
 def _c(x):
@@ -138,6 +139,19 @@ class Engine:
         check(self._lib.crdt_tombstone_gc_async(self._ctx, ctypes.byref(ct), tombs.n_docs, int(R), ptr(stable_vv),
                                                 ctypes.byref(co), _stream(stream)), "crdt_tombstone_gc_async")
 
+    def has_async(self, state: AWSetBatch, queries: QueryBatch, out: QueryBuffers, stream=None):
+        """(*AWSet).Has for each doc's query keys on a device-resident state, with the
+        entry's dot (crdt_awset_has_async); a join / fold / apply output's as_batch() is a state."""
+        s, q, o = _c(state), _c(queries), _c(out)
+        check(self._lib.crdt_awset_has_async(self._ctx, ctypes.byref(s), ctypes.byref(q), ctypes.byref(o),
+                                             _stream(stream)), "crdt_awset_has_async")
+
+    def tomb_has_async(self, tombs: TombBatch, queries: QueryBatch, out: QueryBuffers, stream=None):
+        """The same lookup over each doc's AWSetDelta.Deleted (crdt_tomb_has_async)."""
+        t, q, o = _c(tombs), _c(queries), _c(out)
+        check(self._lib.crdt_tomb_has_async(self._ctx, ctypes.byref(t), tombs.n_docs, ctypes.byref(q),
+                                            ctypes.byref(o), _stream(stream)), "crdt_tomb_has_async")
+
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
               "crdt_vv_min_async")
@@ -232,6 +246,16 @@ class Engine:
                        out.actors[:te], out.counters[:te], out.tomb_off, out.tkeys[:tt], out.tactors[:tt],
                        out.tcounters[:tt])
         return msg, kind[:ns]
+
+    def has(self, state: AWSetBatch, queries: QueryBatch):
+        """Host buffers: (found, actors, counters) numpy arrays, one per query
+        (crdt_awset_has_batch; for tests and small callers)."""
+        state, queries = state.numpy(), queries.numpy()
+        out = QueryBuffers(queries.n_queries)
+        s, q, o = state.c(), queries.c(), out.c()
+        check(self._lib.crdt_awset_has_batch(self._ctx, ctypes.byref(s), ctypes.byref(q), ctypes.byref(o)),
+              "crdt_awset_has_batch")
+        return out.numpy()
 
     def fold(self, mode: int, dst: AWSetBatch, srcs: SrcBatch, pinned: bool = False) -> OutBuffers:
         dst, srcs = dst.numpy(), srcs.numpy()

@@ -42,6 +42,8 @@ hipError_t launch_apply(const BatchView& st, const TombView& tb, const ApplyOps&
                         const TombOut& tout, bool has_tout, const Work& wk, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_extract(const SrcView& sv, const uint64_t* peer, const DeltaOutView& out, uint32_t* gcnt_e,
                           uint32_t* gcnt_t, const Work& wk, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_has(const HasView& sv, const HasQueries& qv, const HasOut& out, uint32_t* status,
+                      const uint32_t* gate, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -657,6 +659,42 @@ int crdt_awset_delta_extract_async(crdt_ctx* ctx, const crdt_src_batch* srcs, co
     rc = hip_err(launch_extract(view(srcs), peer_vv, ov, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(),
                                 make_work(ctx), (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
+}
+
+// Membership reads (query.hip): one launch over the five-array view, ordered
+// after the context's previous call like every call that shares its status word.
+static int has_common(crdt_ctx* ctx, const HasView& sv, const crdt_query_batch* q, const crdt_query_out* out,
+                      void* stream) {
+    if (!q->q_off || !out->found || (q->n_queries && !q->keys) || q->n_docs != sv.n_docs ||
+        (out->actors == nullptr) != (out->counters == nullptr))
+        return CRDT_E_INVALID;
+    if (q->n_queries == 0) return CRDT_OK;
+    if (sv.n_docs == 0) return CRDT_E_INVALID;  // (queries of no document)
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc != CRDT_OK) return rc;
+    const Work wk = make_work(ctx);
+    rc = hip_err(launch_has(sv, HasQueries{q->n_queries, q->q_off, q->keys},
+                            HasOut{out->found, out->actors, out->counters}, wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+int crdt_awset_has_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_query_batch* q,
+                         const crdt_query_out* out, void* stream) {
+    if (!ctx || !state || !q || !out || !state->offsets || state->R == 0 || state->R > CRDT_MAX_R)
+        return CRDT_E_INVALID;
+    return has_common(ctx, HasView{state->n_docs, state->offsets, state->counts, state->keys, state->actors,
+                                   state->counters}, q, out, stream);
+}
+
+int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_docs, const crdt_query_batch* q,
+                        const crdt_query_out* out, void* stream) {
+    if (!ctx || !tombs || !q || !out || !tombs->offsets) return CRDT_E_INVALID;
+    return has_common(ctx, HasView{n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors,
+                                   tombs->counters}, q, out, stream);
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
@@ -1507,6 +1545,62 @@ int crdt_awset_delta_extract_batch(crdt_ctx* ctx, const crdt_src_batch* srcs, co
         if (rc == CRDT_OK) rc = get(out->tcounters, dout.tcounters, tot_t, ctx->stream);
     }
     if (rc == CRDT_OK && out->kind) rc = get(out->kind, dout.kind, ns, ctx->stream);
+    sync = crdt_ctx_sync(ctx, ctx->stream);
+    return rc != CRDT_OK ? rc : sync;
+}
+
+// For tests and small callers (include/crdtgpu.h): the query lists and the slot
+// layout are checked here, the key order on the device; a state out of order
+// reaches no lookup (Work::gate).
+int crdt_awset_has_batch(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_query_batch* q,
+                         const crdt_query_out* out) {
+    if (!ctx || !state || !q || !out || !state->offsets || state->R == 0 || state->R > CRDT_MAX_R)
+        return CRDT_E_INVALID;
+    if (!q->q_off || !out->found || (q->n_queries && !q->keys) || q->n_docs != state->n_docs ||
+        (out->actors == nullptr) != (out->counters == nullptr))
+        return CRDT_E_INVALID;
+    const uint32_t n = state->n_docs, nq = q->n_queries;
+    if (q->q_off[0] != 0 || q->q_off[n] != nq) return CRDT_E_INVALID;
+    for (uint32_t d = 0; d < n; ++d)
+        if (q->q_off[d + 1] < q->q_off[d]) return CRDT_E_INVALID;
+    const bool dots = out->actors != nullptr;
+    for (uint32_t d = 0; d < n; ++d) {
+        const uint32_t o = state->offsets[d], e = state->offsets[d + 1];
+        if (e < o) return CRDT_E_INVALID;
+        if ((state->counts ? state->counts[d] : e - o) > e - o) return CRDT_E_CAPACITY;
+    }
+    const size_t slots = state->offsets[n];
+    if (n && slots > state->offsets[0] && (!state->keys || (dots && (!state->actors || !state->counters))))
+        return CRDT_E_INVALID;
+    if (nq == 0) return CRDT_OK;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    Stager st{ctx};
+    crdt_awset_batch ds = *state;
+    crdt_query_batch dq = *q;
+    st.plan([&] {
+        ds.offsets = st.put(state->offsets, (size_t)n + 1);
+        ds.counts = state->counts ? st.put(state->counts, n) : nullptr;
+        ds.keys = st.put(state->keys, slots);
+        ds.actors = dots ? st.put(state->actors, slots) : nullptr;
+        ds.counters = dots ? st.put(state->counters, slots) : nullptr;
+        dq.q_off = st.put(q->q_off, (size_t)n + 1);
+        dq.keys = st.put(q->keys, nq);
+    });
+    ds.vv = nullptr;  // (not read)
+    crdt_query_out dout{};
+    dout.found = st.room<uint8_t>(nq);
+    dout.actors = dots ? st.room<uint32_t>(nq) : nullptr;
+    dout.counters = dots ? st.room<uint64_t>(nq) : nullptr;
+    st.flush();  // the inputs' span, if they lie in one crdt_host_alloc block
+    if (st.rc != CRDT_OK) return st.rc;
+    rc = check_order(ctx, {{ds.offsets, ds.counts, n, ds.keys}});
+    if (rc == CRDT_OK) rc = gated(ctx, [&] { return crdt_awset_has_async(ctx, &ds, &dq, &dout, ctx->stream); });
+    int sync = crdt_ctx_sync(ctx, ctx->stream);  // (an order violation ends the call here)
+    if (rc != CRDT_OK || sync != CRDT_OK) return rc != CRDT_OK ? rc : sync;
+    rc = get(out->found, dout.found, nq, ctx->stream);
+    if (rc == CRDT_OK && dots) rc = get(out->actors, dout.actors, nq, ctx->stream);
+    if (rc == CRDT_OK && dots) rc = get(out->counters, dout.counters, nq, ctx->stream);
     sync = crdt_ctx_sync(ctx, ctx->stream);
     return rc != CRDT_OK ? rc : sync;
 }

@@ -127,6 +127,30 @@ struct TombOut {
     uint64_t* counters;
 };
 
+// Membership reads (query.hip): the five-array view both lookups read (an AWSet
+// batch without its clocks, or AWSetDelta.Deleted of each document), the
+// per-document query lists and the per-query outputs.
+struct HasView {
+    uint32_t n_docs;
+    const uint32_t* offsets;
+    const uint32_t* counts;
+    const uint64_t* keys;
+    const uint32_t* actors;
+    const uint64_t* counters;
+};
+
+struct HasQueries {
+    uint32_t n_queries;
+    const uint32_t* q_off;
+    const uint64_t* keys;
+};
+
+struct HasOut {
+    uint8_t* found;
+    uint32_t* actors;    // NULL: no dots
+    uint64_t* counters;
+};
+
 // Workspace of the large-document tile path (tile.hip).  A call's tiles are
 // numbered 0 .. total-1 over all its documents and run in passes of at most
 // `cap` tiles (pass p: tiles [p*cap, p*cap + cap)); the per-tile arrays hold

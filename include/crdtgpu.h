@@ -26,6 +26,10 @@
  *       replace the state producers (*AWSet).Add / Del  awset.go:89-101
  *       and (*AWSetDelta).Del                          awset-delta_test.go:14-33
  *       applied as ordered op lists to a batch of documents
+ *   crdt_awset_has_async / crdt_awset_has_batch
+ *       replace (*AWSet).Has                           awset.go:87
+ *       for per-document lists of query keys, with the entry's dot;
+ *       crdt_tomb_has_async is the same lookup over AWSetDelta.Deleted
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -379,6 +383,48 @@ int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const c
                            void* stream);
 int crdt_awset_apply_batch(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
                            const crdt_op_batch* ops, const crdt_awset_out* out, const crdt_tomb_out* tomb_out);
+
+/* ---- membership reads: (*AWSet).Has on device-resident states -------------
+ * Doc d asks the keys q->keys[q_off[d] .. q_off[d+1]).  Per query i of doc d:
+ * found[i] = 1 iff the key equals one of the first counts[d] keys of the doc's
+ * slots (all slots when counts == NULL), awset.go:87; actors[i] / counters[i] =
+ * that entry's dot.  Slots past the live count are never matched, whatever
+ * they hold (the joins pad them with zeros).  For an absent key found, actors
+ * and counters are all 0, so every output word is written.  The VV is not read
+ * (R is validated as elsewhere), so a join, exchange, fold or apply output
+ * (crdt_awset_out with its offsets and counts) is a valid `state` as it
+ * stands.  crdt_tomb_has_async: the same lookup over AWSetDelta.Deleted, "was
+ * k deleted, and by which dot".
+ * _async: one kernel launch, no workspace, no allocation, no host sync
+ * (capturable on an unreserved context), ordered after the context's previous
+ * call; n_queries == 0 launches nothing.  A live count above the doc's slots
+ * is clamped to them and crdt_ctx_sync returns CRDT_E_CAPACITY.
+ * CRDT_E_INVALID: NULL state, q, out, q_off or found, keys NULL with
+ * n_queries > 0, q->n_docs != the state's, exactly one of actors / counters
+ * NULL.
+ * _batch (host arrays; for tests and small callers -- a host caller that holds
+ * host maps looks its keys up there and has no use for it): checks q_off
+ * (q_off[0] == 0, monotone, q_off[n_docs] == n_queries: CRDT_E_INVALID) and the
+ * slot layout and counts (CRDT_E_CAPACITY) on the host, the key order on the
+ * device after the upload (CRDT_E_UNSORTED, no lookup runs), and downloads the
+ * outputs. */
+typedef struct {            /* per-document query lists (read-only) */
+    uint32_t n_docs;        /* must equal the state's n_docs */
+    uint32_t n_queries;     /* == q_off[n_docs]; host-known, as n_slots is for the ingest sort */
+    const uint32_t* q_off;  /* [n_docs+1] doc d asks keys[q_off[d] .. q_off[d+1]) */
+    const uint64_t* keys;   /* [n_queries] any order within a doc, duplicates allowed */
+} crdt_query_batch;
+typedef struct {            /* written, one per query, in query order */
+    uint8_t*  found;        /* [n_queries] 1 = key is a live entry of its doc, else 0 */
+    uint32_t* actors;       /* [n_queries] the entry's dot, 0 when absent; may be NULL */
+    uint64_t* counters;     /* [n_queries] likewise; may be NULL (both or neither) */
+} crdt_query_out;
+int crdt_awset_has_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_query_batch* q,
+                         const crdt_query_out* out, void* stream);
+int crdt_awset_has_batch(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_query_batch* q,
+                         const crdt_query_out* out);
+int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_docs,
+                        const crdt_query_batch* q, const crdt_query_out* out, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
