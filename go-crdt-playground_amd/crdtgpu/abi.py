@@ -33,6 +33,10 @@ CRDT_FOLD_DELTA = 1
 CRDT_DELTA_NONE = 0
 CRDT_DELTA_DELTA = 1
 CRDT_DELTA_FULL = 2
+CRDT_CMP_KEYS = 1
+CRDT_CMP_DOTS = 2
+CRDT_CMP_A_AHEAD = 4
+CRDT_CMP_B_AHEAD = 8
 CRDT_OP_ADD = 0
 CRDT_OP_DEL = 1
 CRDT_OP_DELTA_DEL = 2
@@ -98,6 +102,10 @@ class CQueryBatch(ctypes.Structure):
 
 class CQueryOut(ctypes.Structure):
     _fields_ = [("found", _vp), ("actors", _vp), ("counters", _vp)]
+
+
+class CCompareOut(ctypes.Structure):
+    _fields_ = [("flags", _vp), ("summary", _vp), ("worklist", _vp), ("n_work", _vp)]
 
 
 class CrdtError(RuntimeError):
@@ -174,6 +182,9 @@ def signatures():
         "crdt_awset_has_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CQueryBatch), P(CQueryOut), _vp]),
         "crdt_awset_has_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CQueryBatch), P(CQueryOut)]),
         "crdt_tomb_has_async": (ctypes.c_int, [_vp, P(CTombBatch), _u32, P(CQueryBatch), P(CQueryOut), _vp]),
+        "crdt_awset_compare_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut), _vp]),
+        "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
+        "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

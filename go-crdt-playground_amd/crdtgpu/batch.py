@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CSrcBatch, CTombBatch,
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CSrcBatch, CTombBatch,
                   CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -422,6 +422,41 @@ class QueryBuffers:
         n = self.n_queries
         f = lambda a, dt: None if a is None else _np(a, dt)[:n]  # noqa: E731
         return f(self.found, np.uint8), f(self.actors, U32), f(self.counters, U64)
+
+
+class CompareBuffers:
+    """Outputs of a convergence check (crdt_compare_out): flags (u8 per doc, OR of
+    CRDT_CMP_*), summary (5 counts), worklist (ascending ids of the docs with
+    flags & mask) and n_work (its length, one word -- on the device it feeds
+    select_async as n_idx with no read-back).  numpy, or torch on `device`."""
+
+    def __init__(self, n_docs, device=None, worklist=True, summary=True):
+        self.n_docs = n = int(n_docs)
+        if device is None:
+            self.flags = np.zeros(max(n, 1), np.uint8)
+            self.summary = np.zeros(5, U32) if summary else None
+            self.worklist = np.zeros(max(n, 1), U32) if worklist else None
+            self.n_work = np.zeros(1, U32) if worklist else None
+        else:
+            import torch
+
+            e = lambda k, dt: torch.empty(max(k, 1), dtype=dt, device=device)  # noqa: E731
+            self.flags = e(n, torch.uint8)
+            self.summary = e(5, torch.int32) if summary else None
+            self.worklist = e(n, torch.int32) if worklist else None
+            self.n_work = e(1, torch.int32) if worklist else None
+
+    def c(self) -> CCompareOut:
+        return CCompareOut(ptr(self.flags), ptr(self.summary), ptr(self.worklist), ptr(self.n_work))
+
+    def numpy(self):
+        """(flags [n_docs], summary [5] or None, worklist [n_work] or None) as numpy arrays."""
+        flags = _np(self.flags, np.uint8)[: self.n_docs]
+        summary = None if self.summary is None else _np(self.summary, U32)
+        if self.worklist is None:
+            return flags, summary, None
+        nw = int(_np(self.n_work, U32)[0])
+        return flags, summary, _np(self.worklist, U32)[:nw]
 
 
 def c_ref(x):

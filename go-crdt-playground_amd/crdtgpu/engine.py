@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -152,6 +152,25 @@ class Engine:
         check(self._lib.crdt_tomb_has_async(self._ctx, ctypes.byref(t), tombs.n_docs, ctypes.byref(q),
                                             ctypes.byref(o), _stream(stream)), "crdt_tomb_has_async")
 
+    def compare_async(self, a: AWSetBatch, b: AWSetBatch, out: CompareBuffers, mask: int = 15, stream=None):
+        """Per doc, CRDT_CMP_* of a[d] against b[d] (element sets, dots, clocks), the summary
+        counts and the ascending worklist of docs with flags & mask (crdt_awset_compare_async)."""
+        ca, cb, co = _c(a), _c(b), _c(out)
+        check(self._lib.crdt_awset_compare_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb), int(mask),
+                                                 ctypes.byref(co), _stream(stream)), "crdt_awset_compare_async")
+
+    def select_async(self, state: AWSetBatch, out: OutBuffers, idx=None, n_idx=None, n_out=None, out_slots=None,
+                     stream=None):
+        """out doc j = state doc idx[j] (live entries, count, VV) for j < *n_idx, empty beyond,
+        packed with no slack (crdt_awset_select_async).  idx / n_idx: device u32 arrays (a
+        compare's worklist / n_work); None: the identity / n_out.  All None: compaction."""
+        cs, co = _c(state), _c(out)
+        n_out = out.n_docs if n_out is None else n_out
+        out_slots = out.slots if out_slots is None else out_slots
+        check(self._lib.crdt_awset_select_async(self._ctx, ctypes.byref(cs), ptr(idx), ptr(n_idx), int(n_out),
+                                                int(out_slots), ctypes.byref(co), _stream(stream)),
+              "crdt_awset_select_async")
+
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
               "crdt_vv_min_async")
@@ -255,6 +274,16 @@ class Engine:
         s, q, o = state.c(), queries.c(), out.c()
         check(self._lib.crdt_awset_has_batch(self._ctx, ctypes.byref(s), ctypes.byref(q), ctypes.byref(o)),
               "crdt_awset_has_batch")
+        return out.numpy()
+
+    def compare(self, a: AWSetBatch, b: AWSetBatch, mask: int = 15):
+        """Host buffers: (flags, summary, worklist) numpy arrays (crdt_awset_compare_batch;
+        for tests and small callers)."""
+        a, b = a.numpy(), b.numpy()
+        out = CompareBuffers(a.n_docs)
+        ca, cb, co = a.c(), b.c(), out.c()
+        check(self._lib.crdt_awset_compare_batch(self._ctx, ctypes.byref(ca), ctypes.byref(cb), int(mask),
+                                                 ctypes.byref(co)), "crdt_awset_compare_batch")
         return out.numpy()
 
     def fold(self, mode: int, dst: AWSetBatch, srcs: SrcBatch, pinned: bool = False) -> OutBuffers:

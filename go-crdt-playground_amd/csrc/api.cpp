@@ -44,6 +44,11 @@ hipError_t launch_extract(const SrcView& sv, const uint64_t* peer, const DeltaOu
                           uint32_t* gcnt_t, const Work& wk, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_has(const HasView& sv, const HasQueries& qv, const HasOut& out, uint32_t* status,
                       const uint32_t* gate, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_compare(const BatchView& a, const BatchView& b, uint32_t mask, const CompareOutView& out,
+                          uint32_t* fw, uint32_t* status, const uint32_t* gate, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_select(const BatchView& st, const uint32_t* idx, const uint32_t* n_idx, uint32_t n_out,
+                         uint32_t out_slots, const OutView& out, uint32_t* status, uint32_t n_cu,
+                         hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -511,6 +516,7 @@ int crdt_ctx_sync(crdt_ctx* ctx, void* stream) {
         if (status & kErrActorRange) return CRDT_E_ACTOR_RANGE;
         if (status & kErrWorkspace) return CRDT_E_WORKSPACE;
         if (status & kErrHint) return CRDT_E_INVALID;
+        if (status & kErrIndex) return CRDT_E_INVALID;
         if (status & kErrCapacity) return CRDT_E_CAPACITY;
         if (status & kErrDupKey) return CRDT_E_DUP_KEY;
     }
@@ -695,6 +701,46 @@ int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_
     if (!ctx || !tombs || !q || !out || !tombs->offsets) return CRDT_E_INVALID;
     return has_common(ctx, HasView{n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors,
                                    tombs->counters}, q, out, stream);
+}
+
+// Convergence check (compare.hip).  The per-document flag words the entry and
+// clock passes OR into live in the defer buffer: one word per document, which is
+// what crdt_ctx_reserve(max_docs, ..) sizes it for.
+int crdt_awset_compare_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
+                             const crdt_compare_out* out, void* stream) {
+    if (!ctx || !batch_ptrs_ok(a) || !batch_ptrs_ok(b) || !out || !out->flags) return CRDT_E_INVALID;
+    if (a->n_docs != b->n_docs || a->R != b->R || mask > 15u) return CRDT_E_INVALID;
+    if ((out->worklist == nullptr) != (out->n_work == nullptr)) return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    const Work wk = make_work(ctx);
+    rc = hip_err(launch_compare(view(a), view(b), mask,
+                                CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
+                                ctx->defer.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Sub-batch selection / compaction (compare.hip): no workspace.
+int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const uint32_t* idx, const uint32_t* n_idx,
+                            uint32_t n_out, uint32_t out_slots, const crdt_awset_out* out, void* stream) {
+    if (!ctx || !batch_ptrs_ok(state) || !out_ptrs_ok(out)) return CRDT_E_INVALID;
+    if (out->offsets == state->offsets || out->counts == state->counts || out->keys == state->keys ||
+        out->actors == state->actors || out->counters == state->counters || out->vv == state->vv)
+        return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc != CRDT_OK) return rc;
+    rc = hip_err(launch_select(view(state), idx, n_idx, n_out, out_slots, view(out), make_work(ctx).status,
+                               (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
@@ -1601,6 +1647,47 @@ int crdt_awset_has_batch(crdt_ctx* ctx, const crdt_awset_batch* state, const crd
     rc = get(out->found, dout.found, nq, ctx->stream);
     if (rc == CRDT_OK && dots) rc = get(out->actors, dout.actors, nq, ctx->stream);
     if (rc == CRDT_OK && dots) rc = get(out->counters, dout.counters, nq, ctx->stream);
+    sync = crdt_ctx_sync(ctx, ctx->stream);
+    return rc != CRDT_OK ? rc : sync;
+}
+
+// For tests and small callers (include/crdtgpu.h): the slot layouts are checked
+// here, the key order on the device; batches out of order reach no compare
+// (Work::gate).
+int crdt_awset_compare_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
+                             const crdt_compare_out* out) {
+    if (!ctx || !out || !out->flags) return CRDT_E_INVALID;
+    int rc = validate_batch(a, false);
+    if (rc == CRDT_OK) rc = validate_batch(b, false);
+    if (rc != CRDT_OK) return rc;
+    if (a->n_docs != b->n_docs || a->R != b->R || mask > 15u) return CRDT_E_INVALID;
+    if ((out->worklist == nullptr) != (out->n_work == nullptr)) return CRDT_E_INVALID;
+    const uint32_t n = a->n_docs;
+    if ((rc = set_device(ctx)) != CRDT_OK) return rc;
+    Stager st{ctx};
+    crdt_awset_batch da = *a, db = *b;
+    st.plan([&] {
+        da = stage_batch(st, a);
+        db = stage_batch(st, b);
+    });
+    crdt_compare_out dout{};
+    dout.flags = st.room<uint8_t>(n);
+    dout.summary = out->summary ? st.room<uint32_t>(5) : nullptr;
+    dout.worklist = out->worklist ? st.room<uint32_t>(n) : nullptr;
+    dout.n_work = out->worklist ? st.room<uint32_t>(1) : nullptr;
+    st.flush();  // the inputs' span, if they lie in one crdt_host_alloc block
+    if (st.rc != CRDT_OK) return st.rc;
+    rc = check_order(ctx, {{da.offsets, da.counts, n, da.keys}, {db.offsets, db.counts, n, db.keys}});
+    if (rc == CRDT_OK) rc = gated(ctx, [&] { return crdt_awset_compare_async(ctx, &da, &db, mask, &dout, ctx->stream); });
+    uint32_t nw = 0;
+    if (rc == CRDT_OK && out->worklist) rc = get(&nw, dout.n_work, 1, ctx->stream);
+    int sync = crdt_ctx_sync(ctx, ctx->stream);  // (an order violation ends the call here)
+    if (rc != CRDT_OK || sync != CRDT_OK) return rc != CRDT_OK ? rc : sync;
+    if (nw > n) return CRDT_E_CAPACITY;  // (the list is a subset of the documents: never)
+    rc = get(out->flags, dout.flags, n, ctx->stream);
+    if (rc == CRDT_OK && out->summary) rc = get(out->summary, dout.summary, 5, ctx->stream);
+    if (rc == CRDT_OK && out->worklist) rc = get(out->worklist, dout.worklist, nw, ctx->stream);
+    if (rc == CRDT_OK && out->worklist) *out->n_work = nw;
     sync = crdt_ctx_sync(ctx, ctx->stream);
     return rc != CRDT_OK ? rc : sync;
 }

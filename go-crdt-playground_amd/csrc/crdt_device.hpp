@@ -21,6 +21,7 @@ constexpr uint32_t kErrHint = 4u;       // a doc broke the crdt_ctx_set_max_doc_
 constexpr uint32_t kErrCapacity = 8u;   // a doc's live count exceeds its slots (clamped)
 constexpr uint32_t kErrDupKey = 16u;    // a key appears twice in one document (ingest sort)
 constexpr uint32_t kErrUnsorted = 32u;  // keys not strictly ascending in a document (host path check)
+constexpr uint32_t kErrIndex = 64u;     // a selected document index is not a document of the state (select)
 
 // Kernel-side view of an AWSet batch (same fields as crdt_awset_batch).
 struct BatchView {
@@ -149,6 +150,15 @@ struct HasOut {
     uint8_t* found;
     uint32_t* actors;    // NULL: no dots
     uint64_t* counters;
+};
+
+// Convergence check (compare.hip): what crdt_awset_compare_async writes (same
+// fields as crdt_compare_out).
+struct CompareOutView {
+    uint8_t* flags;
+    uint32_t* summary;   // NULL: none
+    uint32_t* worklist;  // NULL: none (then n_work too)
+    uint32_t* n_work;
 };
 
 // Workspace of the large-document tile path (tile.hip).  A call's tiles are

@@ -30,6 +30,13 @@
  *       replace (*AWSet).Has                           awset.go:87
  *       for per-document lists of query keys, with the entry's dot;
  *       crdt_tomb_has_async is the same lookup over AWSetDelta.Deleted
+ *   crdt_awset_compare_async / crdt_awset_compare_batch
+ *       replace the tests' assertEntries(A, ..) / assertEntries(B, ..): per
+ *       document, do the two replicas hold the same elements, dots and clock;
+ *       with the ascending list of the documents that still differ
+ *   crdt_awset_select_async
+ *       those documents (or all of them: compaction) gathered into a packed
+ *       batch for the next round (no reference counterpart)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -425,6 +432,85 @@ int crdt_awset_has_batch(crdt_ctx* ctx, const crdt_awset_batch* state, const crd
                          const crdt_query_out* out);
 int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_docs,
                         const crdt_query_batch* q, const crdt_query_out* out, void* stream);
+
+/* ---- convergence check: have two replicas converged, and where not --------
+ * The reference's tests end on assertEntries(A, ..) / assertEntries(B, ..), a
+ * comparison of the two replicas' sorted values; crdt_awset_compare_* asks it
+ * of every document of two batches at once.  Comparing clocks is not enough:
+ * (*AWSet).Del does not bump the version vector (awset.go:97), so two replicas
+ * with equal clocks can hold different entries -- the entries are compared.
+ *   - Only the live prefix of each document is read: its first counts[d] slots
+ *     (all slots when counts == NULL).  Slack is never read, whatever it holds.
+ *   - Keys are strictly ascending, so the element sets are equal iff the live
+ *     counts are equal and the keys are equal position by position.
+ *   - CRDT_CMP_KEYS is set iff the element sets are not equal.
+ *   - CRDT_CMP_DOTS is set iff KEYS is clear and some position's (actor,
+ *     counter) differs; it is 0 whenever KEYS is set (not evaluated then; a
+ *     document whose live counts differ has none of its entries read).
+ *   - CRDT_CMP_A_AHEAD / CRDT_CMP_B_AHEAD come from the R clock words alone.
+ *     flags[d] == 0: live state and VV bit-identical.
+ *   - a and b must agree in n_docs and R; their slot layouts are independent.
+ *   - worklist: the ids of the documents with flags & mask != 0, ascending, the
+ *     same on every run (count / scan / emit, no atomic append); words at or past
+ *     *n_work are not written.  summary counts are exact.  mask == 0: an empty
+ *     worklist.
+ *   - A live count above a document's slots is clamped to them and
+ *     crdt_ctx_sync returns CRDT_E_CAPACITY, as in crdt_awset_has_async.
+ *   - CRDT_E_INVALID: NULL a, b, out or flags; n_docs or R mismatch; R out of
+ *     range; exactly one of worklist / n_work NULL; mask bits above 15.
+ *   - n_docs == 0: nothing that reads documents is launched; summary and n_work
+ *     are still written (zeros).
+ * _async: no host sync, and no allocation on a reserved context: its workspace
+ * is one word per document, sized by crdt_ctx_reserve(max_docs, ..)
+ * (CRDT_E_WORKSPACE when it would have to grow during a graph capture).
+ * Capturable; ordered after the context's previous call like every entry point.
+ * After an exchange both outputs hold the same keys, so comparing them leaves
+ * KEYS clear everywhere and only DOTS (a common key under two dots) can remain.
+ * _batch (host arrays; for tests and small callers -- a host caller that holds
+ * host maps compares them there): checks the slot layouts and counts on the
+ * host (CRDT_E_INVALID / CRDT_E_CAPACITY), the key order on the device after the
+ * upload (CRDT_E_UNSORTED, no compare runs), and downloads flags, summary,
+ * n_work and the first *n_work worklist words. */
+#define CRDT_CMP_KEYS    1u /* the element sets differ (what assertEntries tests)            */
+#define CRDT_CMP_DOTS    2u /* same elements, at least one under a different dot             */
+#define CRDT_CMP_A_AHEAD 4u /* a.vv[r] > b.vv[r] for some r < R                              */
+#define CRDT_CMP_B_AHEAD 8u /* b.vv[r] > a.vv[r] for some r < R                              */
+typedef struct {          /* written */
+    uint8_t*  flags;      /* [n_docs] OR of CRDT_CMP_* for doc d; 0 = live state and VV bit-identical */
+    uint32_t* summary;    /* [5] docs with KEYS, DOTS, A_AHEAD, B_AHEAD set, and docs with
+                             flags & mask != 0; may be NULL */
+    uint32_t* worklist;   /* [n_docs] ascending ids of docs with flags & mask != 0; may be NULL */
+    uint32_t* n_work;     /* [1] entries of worklist; NULL iff worklist is NULL */
+} crdt_compare_out;
+int crdt_awset_compare_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
+                             const crdt_compare_out* out, void* stream);
+int crdt_awset_compare_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
+                             const crdt_compare_out* out);
+
+/* ---- select: a subset of documents (or all: compaction) as a packed batch --
+ * out gets n_out documents packed with no slack: out->offsets[j] is the
+ * exclusive prefix of the live counts and offsets[n_out] the total.  For
+ * j < *n_idx, document j is the live entries, count and VV of `state` document
+ * idx[j]; for j >= *n_idx it is empty (count 0, VV zeros).  The result is
+ * directly a valid input batch.  idx (device) may be in any order and may
+ * repeat; idx == NULL is the identity j -> j; n_idx (device, one word) == NULL
+ * means n_out.  idx == NULL, n_idx == NULL and n_out == state->n_docs is the
+ * device-side compaction of a merge output (whose documents sit at capacity
+ * offsets).  *n_idx is read on the device, so the worklist and n_work of
+ * crdt_awset_compare_async feed this call with no host round trip; only
+ * choosing a smaller n_out needs the 4-byte read-back of n_work.
+ * out must hold n_out + 1 offsets, n_out counts, n_out * R clock words and
+ * out_slots entries.  Reported by crdt_ctx_sync:
+ *   *n_idx > n_out       clamped to n_out, CRDT_E_CAPACITY
+ *   total > out_slots    CRDT_E_CAPACITY; nothing is written at or past out_slots
+ *   idx[j] >= n_docs     CRDT_E_INVALID; that document comes out empty
+ *   a live count above the document's slots: clamped, CRDT_E_CAPACITY
+ * out must not alias state: an out array starting where the state's array of
+ * the same kind starts makes the call return CRDT_E_INVALID, as in the exchange.
+ * No workspace, no allocation, no host sync: capturable on any context. */
+int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const uint32_t* idx,
+                            const uint32_t* n_idx /* device, [1] */, uint32_t n_out, uint32_t out_slots,
+                            const crdt_awset_out* out, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
