@@ -185,6 +185,7 @@ def signatures():
         "crdt_awset_compare_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut), _vp]),
         "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
+        "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

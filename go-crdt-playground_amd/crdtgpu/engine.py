@@ -171,6 +171,18 @@ class Engine:
                                                 int(out_slots), ctypes.byref(co), _stream(stream)),
               "crdt_awset_select_async")
 
+    def scatter_async(self, state: AWSetBatch, sub: AWSetBatch, idx, out: OutBuffers, n_idx=None, out_slots=None,
+                      stream=None):
+        """out doc d = sub doc j when idx[j] == d for some j < *n_idx, else state doc d (live
+        entries, count, VV), packed with no slack: select's inverse (crdt_awset_scatter_async).
+        idx / n_idx: device u32 arrays (a compare's worklist / n_work); n_idx None: sub.n_docs.
+        sub is typically the as_batch() of an exchange over the selected sub-batches."""
+        cs, cb, co = _c(state), _c(sub), _c(out)
+        out_slots = out.slots if out_slots is None else out_slots
+        check(self._lib.crdt_awset_scatter_async(self._ctx, ctypes.byref(cs), ctypes.byref(cb), ptr(idx), ptr(n_idx),
+                                                 int(out_slots), ctypes.byref(co), _stream(stream)),
+              "crdt_awset_scatter_async")
+
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
               "crdt_vv_min_async")

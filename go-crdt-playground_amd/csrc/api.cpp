@@ -49,6 +49,9 @@ hipError_t launch_compare(const BatchView& a, const BatchView& b, uint32_t mask,
 hipError_t launch_select(const BatchView& st, const uint32_t* idx, const uint32_t* n_idx, uint32_t n_out,
                          uint32_t out_slots, const OutView& out, uint32_t* status, uint32_t n_cu,
                          hipStream_t stream);
+hipError_t launch_scatter(const BatchView& st, const BatchView& sub, const uint32_t* idx, const uint32_t* n_idx,
+                          uint32_t out_slots, const OutView& out, uint32_t* inv, uint32_t* parts, uint32_t* status,
+                          uint32_t n_cu, hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -740,6 +743,32 @@ int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const 
     if (rc != CRDT_OK) return rc;
     rc = hip_err(launch_select(view(state), idx, n_idx, n_out, out_slots, view(out), make_work(ctx).status,
                                (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Scatter (scatter.hip): the inverse map (one word per state document) lives in
+// the worklist buffer and the scan's partial sums (one word per chunk of
+// documents, at most n_docs) in the defer buffer, which is what
+// crdt_ctx_reserve(max_docs, ..) sizes them for.
+int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_awset_batch* sub,
+                             const uint32_t* idx, const uint32_t* n_idx, uint32_t out_slots, const crdt_awset_out* out,
+                             void* stream) {
+    if (!ctx || !batch_ptrs_ok(state) || !batch_ptrs_ok(sub) || !idx || !out_ptrs_ok(out)) return CRDT_E_INVALID;
+    if (state->R != sub->R) return CRDT_E_INVALID;
+    for (const crdt_awset_batch* b : {state, sub})
+        if (out->offsets == b->offsets || out->counts == b->counts || out->keys == b->keys ||
+            out->actors == b->actors || out->counters == b->counters || out->vv == b->vv)
+            return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(state->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(state->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    rc = hip_err(launch_scatter(view(state), view(sub), idx, n_idx, out_slots, view(out), ctx->worklist.as<uint32_t>(),
+                                ctx->defer.as<uint32_t>(), make_work(ctx).status, (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 

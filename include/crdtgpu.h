@@ -37,6 +37,9 @@
  *   crdt_awset_select_async
  *       those documents (or all of them: compaction) gathered into a packed
  *       batch for the next round (no reference counterpart)
+ *   crdt_awset_scatter_async
+ *       the merged sub-batch written back into the batch it was selected
+ *       from: select's inverse (no reference counterpart)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -511,6 +514,47 @@ int crdt_awset_compare_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const crd
 int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const uint32_t* idx,
                             const uint32_t* n_idx /* device, [1] */, uint32_t n_out, uint32_t out_slots,
                             const crdt_awset_out* out, void* stream);
+
+/* ---- scatter: a merged sub-batch put back into the batch it was selected from
+ * The inverse of select.  out gets state->n_docs documents packed with no
+ * slack: out->offsets[d] is the exclusive prefix of the live counts and
+ * offsets[n_docs] the total.  If idx[j] == d for some j < *n_idx, document d is
+ * the live entries, count and VV of `sub` document j; otherwise it is the live
+ * entries, count and VV of `state` document d.  A replacement may be longer,
+ * shorter or empty, so every later offset moves.  The result is directly a
+ * valid input batch.
+ * state and sub must agree in R; their slot layouts are independent, either may
+ * have counts, slack and documents at capacity offsets (a join, exchange, fold
+ * or apply output is valid as it stands: the crdt_awset_out of an exchange over
+ * a selected sub-batch is the intended `sub`), and only live prefixes are read.
+ * idx (device, sub->n_docs words, required) may be in any order; n_idx (device,
+ * one word) == NULL means sub->n_docs.  *n_idx is read on the device, so the
+ * worklist and n_work of crdt_awset_compare_async feed select, the merge and
+ * this call with no host round trip.  *n_idx == 0 is the identity select of
+ * state.  state->n_docs == 0: offsets[0] = 0 is written and nothing that reads
+ * documents is launched.
+ * out must hold n_docs + 1 offsets, n_docs counts, n_docs * R clock words and
+ * out_slots entries; entry slots at or past the total are not written.
+ * Reported by crdt_ctx_sync:
+ *   *n_idx > sub->n_docs  clamped to sub->n_docs, CRDT_E_CAPACITY
+ *   idx[j] >= n_docs      CRDT_E_INVALID; that sub document is ignored
+ *   two j name one document: CRDT_E_INVALID; the lowest j supplies it, so the
+ *                         output is the same on every run
+ *   total > out_slots     CRDT_E_CAPACITY; nothing is written at or past out_slots
+ *   a live count above its document's slots, on either source: clamped,
+ *                         CRDT_E_CAPACITY
+ * Returned by the call (CRDT_E_INVALID): state, sub, out or idx NULL; R
+ * different between state and sub, or out of range; an out array starting where
+ * the array of the same kind of state or sub starts.
+ * Workspace: one inverse-map word per state document (0xFFFFFFFF = not
+ * replaced) and the partial sums of the offset scan (one word per 1,024
+ * documents), in the context's buffers that crdt_ctx_reserve(max_docs, ..)
+ * sizes: no allocation on a reserved context, CRDT_E_WORKSPACE when they would
+ * have to grow during a graph capture.  No host sync, kernel nodes only,
+ * capturable; ordered after the context's previous call like every entry point. */
+int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_awset_batch* sub,
+                             const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */,
+                             uint32_t out_slots, const crdt_awset_out* out, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
