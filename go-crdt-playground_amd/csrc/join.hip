@@ -40,16 +40,22 @@ struct JoinMeta {
     uint32_t doff, soff, dn, sn, cap;
 };
 
-// Metadata of up to 64 documents, lane i = document first + i*stride: one
-// unconditional vector load per field (indices clamped).
+// Metadata of the wave's cnt <= 64 documents, lane i < cnt = document
+// first + i*stride: one unconditional vector load per field.  Lanes at or past
+// cnt read the wave's first document again (lane 0's addresses: no new
+// traffic) and nobody uses their values.  Indexed by lane alone, the 64 lanes
+// would span 64*stride documents, 1 KB of each array for the 8 documents the
+// wave owns, so every workgroup would also fetch the metadata lines of the
+// seven workgroups after it -- which run on the other XCDs, so each XCD's L2
+// would pull nearly every metadata line of the batch.
 struct MetaVec {
     uint32_t doff, soff, dend, send, dnx, snx;
 };
 
 __device__ __forceinline__ MetaVec meta_vec_issue(const BatchView& dst, const BatchView& src, uint32_t first,
-                                                  uint32_t stride, uint32_t lane) {
+                                                  uint32_t stride, uint32_t cnt, uint32_t lane) {
     const uint32_t n = dst.n_docs;
-    const uint32_t d0 = first + lane * stride;
+    const uint32_t d0 = lane < cnt ? first + lane * stride : first;
     const uint32_t dd = d0 < n ? d0 : n - 1;
     MetaVec v;
     v.doff = dst.offsets[dd];
@@ -306,7 +312,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
     const uint32_t first = uniform(chunk * (WAVES * K) + w);
     if (first >= n_docs) return;
     const uint32_t cnt = min((uint32_t)K, (n_docs - first + WAVES - 1) / WAVES);
-    const MetaVec mv = meta_vec_issue(dst, src, first, WAVES, lane);
+    const MetaVec mv = meta_vec_issue(dst, src, first, WAVES, cnt, lane);
 
     auto push_large = [&](uint32_t dd) {
         if (CRDT_JOIN_WAVE_PUSH) return;  // pushed below, all at once
