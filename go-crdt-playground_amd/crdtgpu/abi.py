@@ -28,6 +28,7 @@ CRDT_E_RCCL = -8
 CRDT_E_DUP_KEY = -9
 CRDT_COMM_ID_BYTES = 128
 CRDT_MAX_R = 64
+CRDT_MAX_REPLICAS = 16
 CRDT_FOLD_AWSET = 0
 CRDT_FOLD_DELTA = 1
 CRDT_DELTA_NONE = 0
@@ -108,6 +109,10 @@ class CCompareOut(ctypes.Structure):
     _fields_ = [("flags", _vp), ("summary", _vp), ("worklist", _vp), ("n_work", _vp)]
 
 
+class CReplica(ctypes.Structure):
+    _fields_ = [("state", _vp), ("tombs", _vp), ("doc_actor", _vp), ("actor", _u32)]
+
+
 class CrdtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -186,6 +191,7 @@ def signatures():
         "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
+        "crdt_awset_sources_async": (ctypes.c_int, [_vp, P(CReplica), _u32, _u32, _u32, P(CDeltaOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

@@ -12,8 +12,8 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CSrcBatch, CTombBatch,
-                  CTombOut)
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CSrcBatch,
+                  CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
 
@@ -361,6 +361,35 @@ class TombBuffers(TombBatch):
 
     def c_out(self) -> CTombOut:
         return CTombOut(ptr(self.offsets), ptr(self.counts), ptr(self.keys), ptr(self.actors), ptr(self.counters))
+
+
+class Replica:
+    """One resident replica of every document (crdt_replica): its state batch, its
+    AWSetDelta.Deleted (tombs, None: none) and its actor -- doc_actor, a u32 per
+    document as in OpBatch, or the scalar `actor` for every document."""
+
+    def __init__(self, state: AWSetBatch, tombs: TombBatch = None, actor: int = 0, doc_actor=None):
+        self.state, self.tombs, self.actor, self.doc_actor = state, tombs, int(actor), doc_actor
+
+    @property
+    def n_docs(self) -> int:
+        return self.state.n_docs
+
+    def c(self) -> CReplica:
+        cs = self.state.c()
+        ct = self.tombs.c() if self.tombs is not None else None
+        r = CReplica(ctypes.addressof(cs), ctypes.addressof(ct) if ct is not None else None, ptr(self.doc_actor),
+                     self.actor)
+        r._keep = (cs, ct)  # the structs the descriptor points at live as long as it does
+        return r
+
+    def numpy(self) -> "Replica":
+        return Replica(self.state.numpy(), self.tombs.numpy() if self.tombs is not None else None, self.actor,
+                       _np(self.doc_actor, U32))
+
+    def to(self, device) -> "Replica":
+        return Replica(self.state.to(device), self.tombs.to(device) if self.tombs is not None else None,
+                       self.actor, _torch(self.doc_actor, device))
 
 
 class QueryBatch:

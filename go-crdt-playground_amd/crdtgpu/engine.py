@@ -183,6 +183,41 @@ class Engine:
                                                  int(out_slots), ctypes.byref(co), _stream(stream)),
               "crdt_awset_scatter_async")
 
+    def sources_async(self, replicas, out: SrcBuffers, entry_slots=None, tomb_slots=None, stream=None):
+        """Resident replicas (a list of Replica, in fold order) gathered into the packed
+        source batch `out`: source d * P + p = replica p's doc d, live entries and
+        tombstones only (crdt_awset_sources_async).  out is then a valid `srcs` of
+        fold_async and delta_extract_async as it stands.  The slot limits default to the
+        sizes of out's entry and tombstone arrays."""
+        cr = [_c(r) for r in replicas]
+        arr = (abi.CReplica * max(len(cr), 1))(*cr)
+        o = out.c_delta_out()
+        if entry_slots is None:
+            entry_slots = int(out.keys.shape[0])
+        if tomb_slots is None:
+            tomb_slots = int(out.tkeys.shape[0]) if out.tkeys is not None else 0
+        check(self._lib.crdt_awset_sources_async(self._ctx, arr, len(cr), int(entry_slots), int(tomb_slots),
+                                                 ctypes.byref(o), _stream(stream)), "crdt_awset_sources_async")
+
+    def sources(self, replicas) -> SrcBatch:
+        """Host replicas uploaded, gathered on the device and the source batch downloaded,
+        trimmed to its packed sizes (for tests and small callers: a caller who holds host
+        data packs it on the host)."""
+        import torch
+
+        reps = [r.numpy() for r in replicas]
+        n, R, P = reps[0].n_docs, reps[0].state.R, len(reps)
+        ne = sum(r.state.live_slots() for r in reps)
+        nt = sum(int(r.tombs.offsets[-1]) - int(r.tombs.offsets[0]) for r in reps if r.tombs is not None)
+        dev = torch.device("cuda", self.device)
+        out = SrcBuffers(R, n, n * P, ne, nt, device=dev)
+        self.sources_async([r.to(dev) for r in reps], out, entry_slots=ne, tomb_slots=nt)
+        self.sync()
+        h = out.numpy()
+        te, tt = int(h.entry_off[-1]), int(h.tomb_off[-1])
+        return SrcBatch(R, h.doc_srcs, h.src_actor, h.vv[: n * P * R], h.entry_off, h.keys[:te], h.actors[:te],
+                        h.counters[:te], h.tomb_off, h.tkeys[:tt], h.tactors[:tt], h.tcounters[:tt])
+
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
               "crdt_vv_min_async")

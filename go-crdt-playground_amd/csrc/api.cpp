@@ -52,6 +52,8 @@ hipError_t launch_select(const BatchView& st, const uint32_t* idx, const uint32_
 hipError_t launch_scatter(const BatchView& st, const BatchView& sub, const uint32_t* idx, const uint32_t* n_idx,
                           uint32_t out_slots, const OutView& out, uint32_t* inv, uint32_t* parts, uint32_t* status,
                           uint32_t n_cu, hipStream_t stream);
+hipError_t launch_sources(const SourcesArgs& s, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status, uint32_t n_cu,
+                          hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -769,6 +771,61 @@ int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const
     if (rc != CRDT_OK) return rc;
     rc = hip_err(launch_scatter(view(state), view(sub), idx, n_idx, out_slots, view(out), ctx->worklist.as<uint32_t>(),
                                 ctx->defer.as<uint32_t>(), make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Sources (sources.hip): the scan's partial sums, one word per 1,024 sources for
+// the entries (worklist buffer) and one for the tombstones (defer buffer).  The
+// replica descriptors are flattened into the kernel arguments here.
+int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n_reps, uint32_t entry_slots,
+                             uint32_t tomb_slots, const crdt_delta_out* out, void* stream) {
+    if (!ctx || !reps || !out || n_reps == 0 || n_reps > CRDT_MAX_REPLICAS) return CRDT_E_INVALID;
+    if (!out->doc_srcs || !out->src_actor || !out->vv || !out->entry_off || !out->keys || !out->actors ||
+        !out->counters)
+        return CRDT_E_INVALID;
+    SourcesArgs a{};
+    for (uint32_t p = 0; p < n_reps; ++p) {
+        const crdt_awset_batch* b = reps[p].state;
+        if (!batch_ptrs_ok(b)) return CRDT_E_INVALID;
+        if (b->n_docs != reps[0].state->n_docs || b->R != reps[0].state->R) return CRDT_E_INVALID;
+        if (out->entry_off == b->offsets || out->keys == b->keys || out->actors == b->actors ||
+            out->counters == b->counters || out->vv == b->vv || (out->src_actor && out->src_actor == reps[p].doc_actor))
+            return CRDT_E_INVALID;
+        SrcRep& r = a.rep[p];
+        r.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
+        r.vv = b->vv;
+        r.doc_actor = reps[p].doc_actor;
+        r.actor = reps[p].actor;
+        if (const crdt_tomb_batch* t = reps[p].tombs) {
+            if (!t->offsets) return CRDT_E_INVALID;
+            if (!out->tomb_off || !out->tkeys || !out->tactors || !out->tcounters) return CRDT_E_INVALID;
+            if (out->tomb_off == t->offsets || out->tkeys == t->keys || out->tactors == t->actors ||
+                out->tcounters == t->counters)
+                return CRDT_E_INVALID;
+            r.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
+        }
+    }
+    const uint64_t n_srcs = (uint64_t)reps[0].state->n_docs * n_reps;
+    if (n_srcs >= (1ull << 32)) return CRDT_E_INVALID;
+    a.n_reps = n_reps;
+    a.n_docs = reps[0].state->n_docs;
+    a.R = reps[0].state->R;
+    a.n_srcs = (uint32_t)n_srcs;
+    a.entry_slots = entry_slots;
+    a.tomb_slots = tomb_slots;
+    a.out = DeltaOutView{out->doc_srcs, out->src_actor, out->vv,    out->entry_off, out->keys,      out->actors,
+                         out->counters, out->tomb_off,  out->tkeys, out->tactors,   out->tcounters, nullptr};
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    const size_t n_parts = (size_t)((n_srcs + 1023) / 1024);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    rc = hip_err(launch_sources(a, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(), make_work(ctx).status,
+                                (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 

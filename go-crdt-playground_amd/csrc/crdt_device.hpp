@@ -74,6 +74,35 @@ struct DeltaOutView {
     uint8_t* kind;  // may be NULL
 };
 
+// Resident replicas gathered into a source batch (sources.hip): the descriptors
+// travel by value in the kernel arguments.
+constexpr int kSrcMaxReps = CRDT_MAX_REPLICAS;
+
+// The five columns of one replica's entries, or of its tombstones (off == NULL: none).
+struct SrcCols {
+    const uint32_t* off;
+    const uint32_t* cnt;
+    const uint64_t* keys;
+    const uint32_t* actors;
+    const uint64_t* counters;
+};
+
+struct SrcRep {
+    SrcCols e, t;
+    const uint64_t* vv;
+    const uint32_t* doc_actor;  // NULL: `actor` for every document
+    uint32_t actor;
+    uint32_t pad;
+};
+
+struct SourcesArgs {
+    SrcRep rep[kSrcMaxReps];  // (unused ones zeroed)
+    uint32_t n_reps, n_docs, R;
+    uint32_t n_srcs;  // n_docs * n_reps
+    uint32_t entry_slots, tomb_slots;
+    DeltaOutView out;
+};
+
 // Scratch copy of the output slots (fold block path ping-pong), `slots` long.
 struct Scratch {
     uint64_t* keys;

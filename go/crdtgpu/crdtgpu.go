@@ -15,6 +15,7 @@
 //	ordered AWSet merges awset.go:103, in order      -> Engine.FoldBatch
 //	(*AWSetDelta).Merge  awset-delta_test.go:51-166  -> Engine.DeltaMerge / DeltaMergeBatch
 //	MakeDeltaMergeData   awset-delta_test.go:79-105  -> Engine.DeltaBatch (what to send a peer)
+//	resident replicas    (no reference counterpart)  -> Engine.SourcesBatch (fold / extraction input on the device)
 //
 // AWSetDelta lives in a _test.go file of the reference, invisible to importers,
 // so this package defines it (with Del and Clone, awset-delta_test.go:9-49).
@@ -615,6 +616,60 @@ func (e *Engine) DeltaBatch(srcs [][]*AWSetDelta, peers []crdt.VersionVector) ([
 		}
 	}
 	return res, nil
+}
+
+// ---------------------------------------------------------------- resident replicas
+
+// Replica is one device-resident replica of every document of a batch: the
+// state batch an apply, join, exchange, fold or scatter call wrote (State, as it
+// stands: offsets, counts, slack), its AWSetDelta.Deleted (Tombs, nil: none) and
+// its actor -- DocActor, a device array of one actor per document, or Actor for
+// every document when DocActor is nil. Every pointer in State and Tombs is a
+// device pointer.
+type Replica struct {
+	State    C.crdt_awset_batch
+	Tombs    *C.crdt_tomb_batch
+	DocActor *C.uint32_t
+	Actor    uint32
+}
+
+// SourcesBatch gathers resident replicas, in fold order, into the packed source
+// batch `out` on the device (crdt_awset_sources_async): source d*len(reps)+p is
+// replica p's document d, live entries and tombstones only. out (device arrays,
+// entrySlots entries and tombSlots tombstones) is then the srcs of a fold or a
+// delta extraction as it stands. The call is asynchronous on stream; device-side
+// errors (a total above the slots) surface at the context's next sync.
+func (e *Engine) SourcesBatch(reps []Replica, entrySlots, tombSlots uint32, out *C.crdt_delta_out,
+	stream unsafe.Pointer) error {
+	if len(reps) == 0 || len(reps) > C.CRDT_MAX_REPLICAS {
+		return fmt.Errorf("SourcesBatch: %d replicas (1..%d)", len(reps), int(C.CRDT_MAX_REPLICAS))
+	}
+	// the descriptors and the structs they point at live in C memory for the call
+	var a arena
+	defer a.free()
+	crSize, stSize := int(unsafe.Sizeof(C.crdt_replica{})), int(unsafe.Sizeof(C.crdt_awset_batch{}))
+	tbSize := int(unsafe.Sizeof(C.crdt_tomb_batch{}))
+	pr, ps, pt := a.alloc(len(reps)*crSize), a.alloc(len(reps)*stSize), a.alloc(len(reps)*tbSize)
+	if a.err != nil {
+		return a.err
+	}
+	crs := unsafe.Slice((*C.crdt_replica)(pr), len(reps))
+	sts := unsafe.Slice((*C.crdt_awset_batch)(ps), len(reps))
+	tbs := unsafe.Slice((*C.crdt_tomb_batch)(pt), len(reps))
+	for i, r := range reps {
+		sts[i] = r.State
+		cr := C.crdt_replica{state: &sts[i], doc_actor: r.DocActor, actor: C.uint32_t(r.Actor)}
+		if r.Tombs != nil {
+			tbs[i] = *r.Tombs
+			cr.tombs = &tbs[i]
+		}
+		crs[i] = cr
+	}
+	if rc := C.crdt_awset_sources_async(e.ctx, &crs[0], C.uint32_t(len(reps)), C.uint32_t(entrySlots),
+		C.uint32_t(tombSlots), out, stream); rc != 0 {
+		return errOf("crdt_awset_sources_async", rc)
+	}
+	return nil
 }
 
 // foldWidth is len(dst.VersionVector) after the fold, replayed on the clocks

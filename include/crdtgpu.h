@@ -40,6 +40,10 @@
  *   crdt_awset_scatter_async
  *       the merged sub-batch written back into the batch it was selected
  *       from: select's inverse (no reference counterpart)
+ *   crdt_awset_sources_async
+ *       P resident replicas of every document gathered into the packed source
+ *       batch the folds and the delta extraction read (no reference
+ *       counterpart: the reference folds replicas it holds as Go values)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -555,6 +559,62 @@ int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const 
 int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_awset_batch* sub,
                              const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */,
                              uint32_t out_slots, const crdt_awset_out* out, void* stream);
+
+/* ---- sources: resident replicas assembled into a fold / extraction input ----
+ * Replicas live on the device as state batches (crdt_awset_batch, plus
+ * crdt_tomb_batch for AWSetDelta.Deleted, plus the replica's actor): the shape
+ * apply, the joins, the folds and scatter write, with offsets, counts and slack.
+ * The folds and the delta extraction read a crdt_src_batch.  This call gathers
+ * n_reps replicas of the same n_docs documents into one packed source batch.
+ * Shape: out describes a source batch with the replicas' common n_docs and R;
+ * doc_srcs[d] = d * n_reps for d <= n_docs; source s = d * n_reps + p is replica
+ * p's document d, so the replica order is the fold order.
+ * Per source: src_actor[s] = reps[p].doc_actor[d], or reps[p].actor when
+ * doc_actor is NULL; vv[s*R..] is the document's clock; the entries are the
+ * document's live prefix (its first counts[d] slots, all slots when counts ==
+ * NULL; slack is never read); the tombstones are the live prefix of `tombs`,
+ * copied verbatim (the re-add filter belongs to the extraction).
+ * Packing: entry_off and tomb_off are exclusive prefixes over all sources, no
+ * slack; entry_off[n_srcs] and tomb_off[n_srcs] are the totals.  Everything
+ * comes out in the order it had, so it stays key-ascending: the result is a
+ * valid `srcs` of crdt_awset_fold_* in both modes and of
+ * crdt_awset_delta_extract_*, as it stands.  A join, exchange, fold, apply or
+ * scatter output is a valid replica state as it stands.
+ * Tombstones: a replica with tombs == NULL contributes empty tombstone ranges.
+ * If every replica has tombs == NULL, out may pass NULL tombstone arrays, and a
+ * tomb_off it does pass is zeroed (the extraction's convention).  out->kind is
+ * never written.
+ * out must hold n_docs + 1 doc_srcs, n_srcs src_actor, n_srcs * R clock words,
+ * n_srcs + 1 entry_off (and tomb_off), entry_slots entries and tomb_slots
+ * tombstones.  Reported by crdt_ctx_sync:
+ *   a live count above its slots, entries or tombstones: clamped, CRDT_E_CAPACITY
+ *   a total above entry_slots or tomb_slots: CRDT_E_CAPACITY; nothing is written
+ *                         at or past those slots (running totals in 64 bits)
+ * Returned by the call (CRDT_E_INVALID): n_reps == 0 or > CRDT_MAX_REPLICAS;
+ * reps, a state or out NULL, or a required out array NULL (the tombstone arrays
+ * are required when some replica has tombs); replicas that disagree in n_docs
+ * or R; R out of range; n_docs * n_reps >= 2^32; an out array starting where
+ * the array of the same kind of any replica starts.
+ * n_docs == 0: doc_srcs[0], entry_off[0] and tomb_off[0] are written as 0 and
+ * nothing that reads documents is launched.
+ * Workspace: the partial sums of the offset scan, two words per 1,024 sources,
+ * in the context's buffers that crdt_ctx_reserve(max_docs, ..) sizes (each holds
+ * max_docs words: enough for 1,024 * max_docs sources): no allocation on a
+ * context reserved for n_srcs / 1,024 documents or more, CRDT_E_WORKSPACE when
+ * they would have to grow during a graph capture.  The replica descriptors
+ * travel in the kernel arguments: no host allocation, no copy call.  No host
+ * sync, kernel nodes only, capturable; ordered after the context's previous
+ * call like every entry point.  There is no _batch form: a caller who holds
+ * host data builds the source batch on the host. */
+#define CRDT_MAX_REPLICAS 16
+typedef struct {                     /* one resident replica of every document (read-only) */
+    const crdt_awset_batch* state;   /* required */
+    const crdt_tomb_batch*  tombs;   /* AWSetDelta.Deleted, or NULL: none */
+    const uint32_t* doc_actor;       /* device [n_docs]: AWSet.Actor per document (as crdt_op_batch), or NULL */
+    uint32_t actor;                  /* used for every document when doc_actor == NULL */
+} crdt_replica;
+int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n_reps, uint32_t entry_slots,
+                             uint32_t tomb_slots, const crdt_delta_out* out, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
