@@ -38,6 +38,8 @@ CRDT_CMP_KEYS = 1
 CRDT_CMP_DOTS = 2
 CRDT_CMP_A_AHEAD = 4
 CRDT_CMP_B_AHEAD = 8
+CRDT_DIG_ELEMENTS = 1
+CRDT_DIG_STATE = 2
 CRDT_OP_ADD = 0
 CRDT_OP_DEL = 1
 CRDT_OP_DELTA_DEL = 2
@@ -189,6 +191,9 @@ def signatures():
         "crdt_tomb_has_async": (ctypes.c_int, [_vp, P(CTombBatch), _u32, P(CQueryBatch), P(CQueryOut), _vp]),
         "crdt_awset_compare_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut), _vp]),
         "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
+        "crdt_awset_digest_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp]),
+        "crdt_awset_digest_host": (ctypes.c_int, [P(CAWSetBatch), P(CTombBatch), _vp]),
+        "crdt_digest_diff_async": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, P(CCompareOut), _vp]),
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_sources_async": (ctypes.c_int, [_vp, P(CReplica), _u32, _u32, _u32, P(CDeltaOut), _vp]),

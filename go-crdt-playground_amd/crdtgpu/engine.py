@@ -159,6 +159,37 @@ class Engine:
         check(self._lib.crdt_awset_compare_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb), int(mask),
                                                  ctypes.byref(co), _stream(stream)), "crdt_awset_compare_async")
 
+    def digest_async(self, state: AWSetBatch, out, tombs: TombBatch = None, stream=None):
+        """Per doc, the 16-byte digest of its live state into `out` (device u64 [2 * n_docs]):
+        word 0 the element set, word 1 elements, dots, Deleted and clock
+        (crdt_awset_digest_async); a join / fold / apply output's as_batch() is a state."""
+        s = _c(state)
+        t = _c(tombs) if tombs is not None else None
+        check(self._lib.crdt_awset_digest_async(self._ctx, ctypes.byref(s), ctypes.byref(t) if t else None, ptr(out),
+                                                _stream(stream)), "crdt_awset_digest_async")
+
+    def digest(self, state: AWSetBatch, tombs: TombBatch = None):
+        """Host batch uploaded and digested on the device: numpy u64 [n_docs, 2] (for tests
+        and small callers: a caller who holds host data uses digest_host)."""
+        import numpy as np
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        state = state.numpy()
+        out = torch.empty(max(2 * state.n_docs, 1), dtype=torch.int64, device=dev)
+        ds, dt = state.to(dev), tombs.numpy().to(dev) if tombs is not None else None
+        self.digest_async(ds, out, dt)
+        self.sync()
+        return _np(out, np.uint64)[: 2 * state.n_docs].reshape(state.n_docs, 2)
+
+    def digest_diff_async(self, mine, theirs, n_docs: int, out: CompareBuffers, mask: int = 3, stream=None):
+        """Per doc, CRDT_DIG_ELEMENTS / CRDT_DIG_STATE of two digest arrays (device u64
+        [2 * n_docs]), the summary counts and the ascending worklist of docs with flags & mask,
+        as compare_async writes them (crdt_digest_diff_async)."""
+        co = _c(out)
+        check(self._lib.crdt_digest_diff_async(self._ctx, ptr(mine), ptr(theirs), int(n_docs), int(mask),
+                                               ctypes.byref(co), _stream(stream)), "crdt_digest_diff_async")
+
     def select_async(self, state: AWSetBatch, out: OutBuffers, idx=None, n_idx=None, n_out=None, out_slots=None,
                      stream=None):
         """out doc j = state doc idx[j] (live entries, count, VV) for j < *n_idx, empty beyond,
@@ -410,6 +441,21 @@ def zipf_sizes(seed: int, n_docs: int):
     out = np.zeros(max(n_docs, 1), dtype=np.uint32)
     check(abi.lib().crdt_gen_zipf_sizes(int(seed), int(n_docs), out.ctypes.data), "crdt_gen_zipf_sizes")
     return out[:n_docs]
+
+
+def digest_host(batch: AWSetBatch, tombs: TombBatch = None):
+    """Per-doc digests of a host batch, numpy u64 [n_docs, 2] (crdt_awset_digest_host: no
+    GPU; a doc's entries may lie in any order).  Raises CrdtError on a bad layout."""
+    import numpy as np
+
+    b = batch.numpy()
+    cb = b.c()
+    t = tombs.numpy() if tombs is not None else None
+    ct = t.c() if t is not None else None
+    out = np.zeros(max(2 * b.n_docs, 1), dtype=np.uint64)
+    check(abi.lib().crdt_awset_digest_host(ctypes.byref(cb), ctypes.byref(ct) if ct else None, out.ctypes.data),
+          "crdt_awset_digest_host")
+    return out[: 2 * b.n_docs].reshape(b.n_docs, 2)
 
 
 def validate(batch: AWSetBatch) -> int:

@@ -54,6 +54,11 @@ hipError_t launch_scatter(const BatchView& st, const BatchView& sub, const uint3
                           uint32_t n_cu, hipStream_t stream);
 hipError_t launch_sources(const SourcesArgs& s, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status, uint32_t n_cu,
                           hipStream_t stream);
+hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
+                         uint32_t* status, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
+                              const CompareOutView& out, uint32_t* fw, const uint32_t* gate, uint32_t n_cu,
+                              hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -727,6 +732,52 @@ int crdt_awset_compare_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crd
     rc = hip_err(launch_compare(view(a), view(b), mask,
                                 CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
                                 ctx->defer.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// State digests (digest.hip): the digest words are the accumulators, no workspace.
+int crdt_awset_digest_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
+                            uint64_t* digest, void* stream) {
+    if (!ctx || !batch_ptrs_ok(state) || !digest || (tombs && !tombs->offsets)) return CRDT_E_INVALID;
+    for (const void* p : {(const void*)state->offsets, (const void*)state->counts, (const void*)state->keys,
+                          (const void*)state->actors, (const void*)state->counters, (const void*)state->vv})
+        if (p == digest) return CRDT_E_INVALID;
+    if (tombs)
+        for (const void* p : {(const void*)tombs->offsets, (const void*)tombs->counts, (const void*)tombs->keys,
+                              (const void*)tombs->actors, (const void*)tombs->counters})
+            if (p == digest) return CRDT_E_INVALID;
+    if (state->n_docs == 0) return CRDT_OK;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc != CRDT_OK) return rc;
+    const HasView sv{state->n_docs, state->offsets, state->counts, state->keys, state->actors, state->counters};
+    const HasView tv = tombs ? HasView{state->n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors,
+                                       tombs->counters}
+                             : HasView{state->n_docs, nullptr, nullptr, nullptr, nullptr, nullptr};
+    rc = hip_err(launch_digest(sv, tv, state->vv, state->R, digest, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Digest comparison (digest.hip, then compare.hip's worklist step): the flag
+// words live in the defer buffer, one per document, as in the compare.
+int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* theirs, uint32_t n_docs, uint32_t mask,
+                           const crdt_compare_out* out, void* stream) {
+    if (!ctx || !out || !out->flags || mask > 15u) return CRDT_E_INVALID;
+    if (n_docs && (!mine || !theirs)) return CRDT_E_INVALID;
+    if ((out->worklist == nullptr) != (out->n_work == nullptr)) return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    rc = hip_err(launch_digest_diff(mine, theirs, n_docs, mask,
+                                    CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
+                                    ctx->defer.as<uint32_t>(), make_work(ctx).gate, (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 

@@ -584,6 +584,13 @@ __global__ __launch_bounds__(kCmpNT) void select_gather_kernel(SelectArgs s, uin
 
 static bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// The worklist step alone, over n flag words another launch wrote (also digest.hip's diff).
+hipError_t launch_worklist(const uint32_t* fw, uint32_t n, uint32_t mask, const CompareOutView& out,
+                           const uint32_t* gate, hipStream_t stream) {
+    hipLaunchKernelGGL(compare_worklist_kernel, dim3(1), dim3(kScanNT), 0, stream, fw, n, mask, out, gate);
+    return hipGetLastError();
+}
+
 // fw: n_docs workspace words.  n_docs == 0: only the summary and n_work are written.
 hipError_t launch_compare(const BatchView& a, const BatchView& b, uint32_t mask, const CompareOutView& out,
                           uint32_t* fw, uint32_t* status, const uint32_t* gate, uint32_t n_cu, hipStream_t stream) {
@@ -599,8 +606,7 @@ hipError_t launch_compare(const BatchView& a, const BatchView& b, uint32_t mask,
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(compare_worklist_kernel, dim3(1), dim3(kScanNT), 0, stream, fw, n, mask, out, gate);
-    return hipGetLastError();
+    return launch_worklist(fw, n, mask, out, gate, stream);
 }
 
 hipError_t launch_select(const BatchView& st, const uint32_t* idx, const uint32_t* n_idx, uint32_t n_out,

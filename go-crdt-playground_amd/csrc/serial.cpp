@@ -8,6 +8,10 @@
 //   crdt_batch_dump / crdt_batch_info / crdt_batch_undump
 //                       a self-checking binary image of a batch (live entries
 //                       only, compact offsets), for fixtures and diffing
+//   crdt_awset_digest_host
+//                       the per-document state digest of a host batch: the C
+//                       statement of the definition the kernels (digest.hip)
+//                       compute, for a peer that holds host maps
 //
 // Host buffers only; no GPU.
 #include <cstdint>
@@ -16,6 +20,7 @@
 #include <vector>
 
 #include "../../include/crdtgpu.h"
+#include "digest_hash.hpp"
 
 namespace {
 
@@ -160,6 +165,19 @@ uint32_t live_of(const crdt_awset_batch* b, uint32_t d) {
     return b->counts ? b->counts[d] : b->offsets[d + 1] - b->offsets[d];
 }
 
+// Slot layout of n_docs documents (entries or tombstones): monotone offsets,
+// live counts within the slots, arrays present when there is a slot.
+int check_layout(uint32_t n_docs, const uint32_t* offsets, const uint32_t* counts, const uint64_t* keys,
+                 const uint32_t* actors, const uint64_t* counters) {
+    if (!offsets) return CRDT_E_INVALID;
+    if (n_docs && offsets[n_docs] > offsets[0] && (!keys || !actors || !counters)) return CRDT_E_INVALID;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        if (offsets[d + 1] < offsets[d]) return CRDT_E_INVALID;
+        if (counts && counts[d] > offsets[d + 1] - offsets[d]) return CRDT_E_CAPACITY;
+    }
+    return CRDT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -284,6 +302,39 @@ int crdt_batch_undump(const void* buf, size_t len, const crdt_awset_out* out) {
     memcpy(out->counters, q + 8 * n, 8 * n);
     memcpy(out->actors, q + 16 * n, 4 * n);
     memcpy(out->vv, q + ents_bytes(n), 8 * (size_t)nd * r);
+    return CRDT_OK;
+}
+
+// The definition of the state digest (include/crdtgpu.h), document by document
+// and entry by entry in the order they lie: the sums commute, so no order is
+// required of the keys.
+int crdt_awset_digest_host(const crdt_awset_batch* state, const crdt_tomb_batch* tombs, uint64_t* digest) {
+    using namespace crdt;
+    if (!state || !digest || state->R == 0 || state->R > CRDT_MAX_R) return CRDT_E_INVALID;
+    if (state->n_docs && !state->vv) return CRDT_E_INVALID;
+    const uint32_t n_docs = state->n_docs, R = state->R;
+    int rc = check_layout(n_docs, state->offsets, state->counts, state->keys, state->actors, state->counters);
+    if (rc == CRDT_OK && tombs)
+        rc = check_layout(n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors, tombs->counters);
+    if (rc != CRDT_OK) return rc;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const uint32_t o = state->offsets[d], n = live_of(state, d);
+        uint64_t w0 = 0, w1 = 0, m = 0;
+        for (uint32_t i = o; i < o + n; ++i) {
+            const uint64_t hk = dig_key(state->keys[i]);
+            w0 += hk;
+            w1 += dig_dot(hk, state->actors[i], state->counters[i]);
+        }
+        if (tombs) {
+            const uint32_t to = tombs->offsets[d];
+            m = tombs->counts ? tombs->counts[d] : tombs->offsets[d + 1] - to;
+            for (uint32_t i = to; i < to + (uint32_t)m; ++i)
+                w1 += dig_dot(dig_fmix(tombs->keys[i] + kDigT), tombs->actors[i], tombs->counters[i]);
+        }
+        for (uint32_t r = 0; r < R; ++r) w1 += dig_clock(r, state->vv[(size_t)d * R + r]);
+        digest[2 * (size_t)d] = dig_fmix(w0 + kDigN * n);
+        digest[2 * (size_t)d + 1] = dig_fmix(w1 + kDigN * (n + m));
+    }
     return CRDT_OK;
 }
 

@@ -672,6 +672,35 @@ func (e *Engine) SourcesBatch(reps []Replica, entrySlots, tombSlots uint32, out 
 	return nil
 }
 
+// ---------------------------------------------------------------- state digests
+
+// HostBatch is a packed batch in host memory: State as arena.batch lays it out
+// (or any crdt_awset_batch over host arrays; a document's entries may lie in any
+// order, so a map can be packed in iteration order) and its AWSetDelta.Deleted
+// (Tombs, nil: none).
+type HostBatch struct {
+	State C.crdt_awset_batch
+	Tombs *C.crdt_tomb_batch
+}
+
+// Digest is the 16-byte state digest of every document (crdt_awset_digest_host,
+// no GPU): [d][0] covers the element set, [d][1] elements, dots, Deleted and
+// clock. A peer compares these with the digests a device computed
+// (crdt_awset_digest_async) to find the documents that differ, provided both
+// share the key interning.
+func (b *HostBatch) Digest() ([][2]uint64, error) {
+	n := int(b.State.n_docs)
+	flat := make([]uint64, 2*n+2)
+	if rc := C.crdt_awset_digest_host(&b.State, b.Tombs, p64(flat)); rc != 0 {
+		return nil, errOf("crdt_awset_digest_host", rc)
+	}
+	out := make([][2]uint64, n)
+	for d := range out {
+		out[d] = [2]uint64{flat[2*d], flat[2*d+1]}
+	}
+	return out, nil
+}
+
 // foldWidth is len(dst.VersionVector) after the fold, replayed on the clocks
 // alone: every AWSet step merges the clock; a delta step merges it unless it
 // is the no-op (awset-delta_test.go:60): Counter(src.Actor) != 0 (:53) and

@@ -34,6 +34,10 @@
  *       replace the tests' assertEntries(A, ..) / assertEntries(B, ..): per
  *       document, do the two replicas hold the same elements, dots and clock;
  *       with the ascending list of the documents that still differ
+ *   crdt_awset_digest_async / crdt_awset_digest_host / crdt_digest_diff_async
+ *       the same question across GPUs or hosts: a 16-byte hash of each
+ *       document's live state, and the comparison of two such arrays (no
+ *       reference counterpart: its replicas meet in one process)
  *   crdt_awset_select_async
  *       those documents (or all of them: compaction) gathered into a packed
  *       batch for the next round (no reference counterpart)
@@ -493,6 +497,78 @@ int crdt_awset_compare_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crd
                              const crdt_compare_out* out, void* stream);
 int crdt_awset_compare_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
                              const crdt_compare_out* out);
+
+/* ---- state digests: which documents differ from a peer's copy elsewhere -----
+ * crdt_awset_compare_* needs both replicas on one device.  Between GPUs or
+ * hosts a peer ships 16 B per document instead of its states: a digest of the
+ * live state, diffed against the local one; the resulting worklist feeds
+ * select, sources, the delta extraction and the folds.  Clocks cannot stand in
+ * for it: (*AWSet).Del does not bump the version vector (awset.go:97).
+ * The definition is part of the ABI and does not change.  All arithmetic is mod
+ * 2^64; fmix is the splitmix64 finaliser:
+ *   fmix(x): x ^= x>>30; x *= 0xBF58476D1CE4E5B9; x ^= x>>27;
+ *            x *= 0x94D049BB133111EB; x ^= x>>31
+ *   K_E = 0x9E3779B97F4A7C15  K_T = 0xC2B2AE3D27D4EB4F  K_A = 0xD6E8FEB86659FD93
+ *   K_V = 0x165667B19E3779F9  K_N = 0x85EBCA77C2B2AE63
+ *   hk(k)     = fmix(k + K_E)
+ *   hd(k,a,c) = fmix(hk(k) ^ (c + K_A*(a+1)))           live entry k -> dot (a,c)
+ *   ht(k,a,c) = fmix(fmix(k + K_T) ^ (c + K_A*(a+1)))   live tombstone (AWSetDelta.Deleted)
+ *   hv(r,v)   = v == 0 ? 0 : fmix(v + K_V*(r+1))        clock word r
+ * Document d with n live entries, m live tombstones and clock vv[0..R):
+ *   digest[2d]   = fmix(sum hk + K_N*n)                      the element set (what
+ *                                                            assertEntries tests)
+ *   digest[2d+1] = fmix(sum hd + sum ht + sum hv + K_N*(n+m))  elements, dots,
+ *                                                            Deleted and clock
+ *   - Live prefix only: the first counts[d] slots of a document (all slots when
+ *     counts == NULL), entries and tombstones alike.  Slack is never read.  A
+ *     live count above the slots is clamped to them and crdt_ctx_sync returns
+ *     CRDT_E_CAPACITY, as in crdt_awset_has_async.
+ *   - The sums commute: the digest does not depend on the order of a document's
+ *     entries, nor on how the device cuts the work up, so it is bit-identical
+ *     on every run, and a host peer may hash a Go map in iteration order
+ *     without sorting.
+ *   - A zero clock word contributes nothing, so the digest does not depend on
+ *     the R padding: [5,0] at R = 2 and [5,0,0,0] at R = 4 digest alike (the
+ *     reference's VersionVectors are ragged; peers need not agree on R).
+ *   - tombs == NULL, and a tomb batch whose documents are all empty, digest
+ *     alike: an AWSet and an AWSetDelta with an empty Deleted agree.
+ *   - Tombstones collected on one side only (crdt_tombstone_gc_async) change
+ *     word 1 and never word 0: compare word 0 if you GC independently.
+ *   - Digests are comparable only between peers that share the key interning,
+ *     like everything else here.
+ *   - An empty document with a zero clock digests to (0, 0).
+ * crdt_awset_digest_async: digest is [2*n_docs] u64 on the device.  A join,
+ * exchange, fold, apply or scatter output is a valid `state` as it stands.  The
+ * digest words are the accumulators: no workspace, no allocation, no host sync,
+ * kernel nodes only, capturable on an unreserved context; ordered after the
+ * context's previous call like every entry point.  n_docs == 0 launches nothing.
+ * CRDT_E_INVALID: NULL state or digest, R out of range, tombs without offsets,
+ * digest starting where an input array starts.
+ * crdt_awset_digest_host: the same definition over host arrays, no GPU and no
+ * context, for the peer that holds host maps; a document's entries may lie in
+ * ANY order.  The slot layout and the counts are checked (CRDT_E_INVALID: NULL
+ * arrays, R out of range, offsets not monotone; CRDT_E_CAPACITY: a live count
+ * above its slots; nothing is clamped here).
+ * crdt_digest_diff_async: mine and theirs are [2*n_docs] u64 on the device; out
+ * is written as by crdt_awset_compare_async with
+ *   flags[d]   CRDT_DIG_ELEMENTS when word 0 differs, else CRDT_DIG_STATE when
+ *              word 1 differs, else 0 (STATE is 0 whenever ELEMENTS is set)
+ *   summary    [0] documents with ELEMENTS, [1] with STATE, [2] and [3] zero,
+ *              [4] documents with flags & mask
+ *   worklist   ascending, the same on every run, untouched at or past *n_work
+ * so the worklist and n_work feed crdt_awset_select_async with no host round
+ * trip.  Validation, n_docs == 0 (summary and n_work still written) and the
+ * workspace (one word per document, crdt_ctx_reserve(max_docs, ..);
+ * CRDT_E_WORKSPACE under capture) are those of crdt_awset_compare_async; mine
+ * and theirs may be NULL only when n_docs == 0. */
+#define CRDT_DIG_ELEMENTS 1u /* word 0 differs                       (== CRDT_CMP_KEYS) */
+#define CRDT_DIG_STATE    2u /* word 0 equal, word 1 differs         (== CRDT_CMP_DOTS) */
+int crdt_awset_digest_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs /* or NULL */,
+                            uint64_t* digest, void* stream);
+int crdt_awset_digest_host(const crdt_awset_batch* state, const crdt_tomb_batch* tombs /* or NULL */,
+                           uint64_t* digest);
+int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* theirs, uint32_t n_docs, uint32_t mask,
+                           const crdt_compare_out* out, void* stream);
 
 /* ---- select: a subset of documents (or all: compaction) as a packed batch --
  * out gets n_out documents packed with no slack: out->offsets[j] is the
