@@ -85,7 +85,13 @@ def random_history(rng: random.Random, R: int, n_ops: int, n_keys: int, delta: b
 
 
 def random_state(rng: random.Random, R: int, n: int, universe: int, max_counter: int, actor_hi=None):
-    """Arbitrary (not necessarily reachable) AWSet state: keys, dots and VV at random."""
+    """Arbitrary (not necessarily reachable) AWSet state: keys, dots and VV at random.
+
+    max_counter stays small in the base cases (6 ... 50) on purpose: the merge
+    path only orders counters, so tests/counter_maps.py pushes these same cases
+    through strictly increasing tables over 0..64 up to the 2^31, 2^32, 2^63 and
+    2^64 - 1 edges (tests/test_gpu_wide_counters.py), and a case stays usable
+    there as long as its counters fit a table (max_counter <= 64)."""
     actor_hi = R - 1 if actor_hi is None else actor_hi
     keys = sorted(rng.sample(range(universe), n))
     e = [(k, rng.randint(0, actor_hi), rng.randint(1, max_counter)) for k in keys]

@@ -48,24 +48,37 @@ def test_vv_min(eng, torch):
     assert (da.cpu().numpy().view(np.uint64) == np.minimum(a, b)).all()
 
 
-@pytest.mark.parametrize("R", [2, 8, 64])
-def test_tombstone_gc_matches_oracle(eng, torch, R):
+def gc_case(R, n=4000):
+    """(tombstones per doc, stable clocks [n * R]): lists of 0 ... 300 tombstones, actors up to R + 1."""
     rng = random.Random(R)
-    per_doc, n = [], 4000
+    per_doc = []
     for _ in range(n):
         keys = sorted(rng.sample(range(10 ** 6), rng.choice([0, 1, 3, 63, 64, 65, 300])))
         per_doc.append([(k, rng.randrange(R + 2), rng.randint(1, 50)) for k in keys])  # actors >= R kept
-    tb = TombBatch.from_lists(per_doc)
     stable = np.array([rng.randint(0, 50) for _ in range(n * R)], dtype=np.uint64)
-    rc, want = oracle.tomb_gc(tb, R, stable)
-    assert rc == 0
+    return per_doc, stable
+
+
+def gc_on_gpu(eng, torch, tb, R, stable):
+    """crdt_tombstone_gc_async on device copies; the output as a host TombBatch."""
     dev = torch.device("cuda:0")
+    n = tb.n_docs
     out = TombBuffers(n, int(tb.offsets[-1]), device=dev)
     eng.tombstone_gc_async(tb.to(dev), R, _i64(stable, torch, dev), out)
     eng.sync()
-    got = TombBatch(*(t.cpu().numpy().view(np.uint32 if t.dtype == torch.int32 else np.uint64)
-                      for t in (out.offsets, out.keys, out.actors, out.counters)),
-                    counts=out.counts.cpu().numpy().view(np.uint32))
+    return TombBatch(*(t.cpu().numpy().view(np.uint32 if t.dtype == torch.int32 else np.uint64)
+                       for t in (out.offsets, out.keys, out.actors, out.counters)),
+                     counts=out.counts.cpu().numpy().view(np.uint32))
+
+
+@pytest.mark.parametrize("R", [2, 8, 64])
+def test_tombstone_gc_matches_oracle(eng, torch, R):
+    n = 4000
+    per_doc, stable = gc_case(R, n)
+    tb = TombBatch.from_lists(per_doc)
+    rc, want = oracle.tomb_gc(tb, R, stable)
+    assert rc == 0
+    got = gc_on_gpu(eng, torch, tb, R, stable)
     assert (got.offsets == want.offsets).all()
     for d in range(n):
         assert got.doc(d) == want.doc(d), d

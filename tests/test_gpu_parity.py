@@ -235,21 +235,17 @@ def test_fold_block_path_and_overflow(eng, mode):
     assert_same(eng.fold(mode, dst, srcs), want, dst.n_docs, R)
 
 
-@pytest.mark.parametrize("mode", [CRDT_FOLD_AWSET, CRDT_FOLD_DELTA])
-def test_fold_wide_key_spans(eng, mode):
-    """The in-register sort packs (key, tag) into 32 bits when a document's keys
-    lie within 2^15 of its first kept key, into 64 bits within 2^47, and falls
-    back to the 80-bit comparison beyond: every tier, mixed in one batch, and
-    keys at both ends of the u64 range."""
+def wide_key_case(mode, n_docs=1200):
+    """(R, dst docs, sources per doc): per-document monotone key maps -- dense,
+    spread beyond 2^16, beyond 2^48, the whole u64 range -- over small random states."""
     rng = random.Random(40 + mode)
     R = 4
     delta = mode == CRDT_FOLD_DELTA
     top = (1 << 64) - 1
-    # per-document monotone key maps: dense, spread beyond 2^16, beyond 2^48, the whole range
     maps = [lambda k: k, lambda k: (1 << 40) + k * 1021, lambda k: (1 << 62) + k * (1 << 41),
             lambda k: min(top, k * (top // 199))]
     dsts, per_doc = [], []
-    for d in range(1200):
+    for d in range(n_docs):
         f = maps[d % len(maps)]
         mp = lambda es: [(f(k), a, c) for k, a, c in es]
         e, vv = random_state(rng, R, rng.randint(0, 64), 200, 8)
@@ -260,23 +256,30 @@ def test_fold_wide_key_spans(eng, mode):
             t = mp(random_state(rng, R, rng.randint(0, 3), 200, 8)[0]) if delta else []
             chain.append((rng.randrange(R), svv, mp(se), t))
         per_doc.append(chain)
+    return R, dsts, per_doc
+
+
+@pytest.mark.parametrize("mode", [CRDT_FOLD_AWSET, CRDT_FOLD_DELTA])
+def test_fold_wide_key_spans(eng, mode):
+    """The in-register sort packs (key, tag) into 32 bits when a document's keys
+    lie within 2^15 of its first kept key, into 64 bits within 2^47, and falls
+    back to the 80-bit comparison beyond: every tier, mixed in one batch, and
+    keys at both ends of the u64 range."""
+    R, dsts, per_doc = wide_key_case(mode)
     dst, srcs = batch_of(R, dsts), src_batch_of(R, per_doc)
     rc, want = oracle.fold(mode, dst, srcs)
     assert rc == 0
     assert_same(eng.fold(mode, dst, srcs), want, dst.n_docs, R)
 
 
-@pytest.mark.parametrize("lean", [1, 0])
-def test_delta_fold_lean_pass_defers(eng, lean):
-    """Delta folds run a lean slot-walk pass first (fold.hip LEAN) and defer every
-    document it cannot walk to the general kernel: interleaved in one batch,
-    dense documents next to key spans >= 256, 16+ sources, clocks beyond the lean
-    pass's 192 words (R = 16 x 13 sources), tuples beyond 256 (block path) and
-    empty documents -- the same bits as the general kernel alone and the oracle."""
+def lean_defer_case(n_docs=3000):
+    """(R, dst docs, sources per doc) of six kinds of document interleaved: dense,
+    key spans >= 256, 16 sources, R = 16 x 13 sources (clocks beyond the lean
+    pass's 192 words), more than 256 tuples (block path), and empty."""
     rng = random.Random(77)
     R = 16
     dsts, per_doc = [], []
-    for d in range(3000):
+    for d in range(n_docs):
         kind = d % 6
         universe = 200 if kind == 0 else (5000 if kind == 1 else 150)
         n_src = {0: rng.randint(0, 10), 1: rng.randint(0, 8), 2: 16, 3: 13, 4: 3, 5: 0}[kind]
@@ -289,6 +292,17 @@ def test_delta_fold_lean_pass_defers(eng, lean):
             t = random_state(rng, R, rng.randint(0, 3), universe, 9)[0]
             chain.append((rng.randrange(R), vv, e, t))
         per_doc.append(chain)
+    return R, dsts, per_doc
+
+
+@pytest.mark.parametrize("lean", [1, 0])
+def test_delta_fold_lean_pass_defers(eng, lean):
+    """Delta folds run a lean slot-walk pass first (fold.hip LEAN) and defer every
+    document it cannot walk to the general kernel: interleaved in one batch,
+    dense documents next to key spans >= 256, 16+ sources, clocks beyond the lean
+    pass's 192 words (R = 16 x 13 sources), tuples beyond 256 (block path) and
+    empty documents -- the same bits as the general kernel alone and the oracle."""
+    R, dsts, per_doc = lean_defer_case()
     dst, srcs = batch_of(R, dsts), src_batch_of(R, per_doc)
     rc, want = oracle.fold(CRDT_FOLD_DELTA, dst, srcs)
     assert rc == 0
@@ -299,21 +313,20 @@ def test_delta_fold_lean_pass_defers(eng, lean):
         eng.set_option("fold_lean_first", 1)
 
 
-@pytest.mark.parametrize("mode", [CRDT_FOLD_AWSET, CRDT_FOLD_DELTA])
-def test_fold_panic_parity_per_doc(eng, mode):
-    """actor == len(VV) panics exactly where the reference evaluates HasDot on
-    it (a full step's add check, a tombstone's check, a gap step's removal
-    check, the path select), and actor > len(VV) is "never seen": one
-    document per call, the oracle's verdict against the kernel's."""
-    rng = random.Random(50 + mode)
-    R = 3
-    delta = mode == CRDT_FOLD_DELTA
-    seen_err = seen_ok = 0
+PANIC_R = 3
 
-    def ah():  # now and then a state whose dots name actors R and R + 1
+
+def panic_cases(mode, n=240):
+    """n single documents (dst entries, dst clock, source chain), R = PANIC_R: now and
+    then a state whose dots name actors R and R + 1, a source actor R, a zeroed clock entry."""
+    rng = random.Random(50 + mode)
+    R = PANIC_R
+    delta = mode == CRDT_FOLD_DELTA
+
+    def ah():
         return R + 1 if rng.random() < 0.12 else None
 
-    for _ in range(240):
+    for _ in range(n):
         e, vv = random_state(rng, R, rng.randint(0, 12), 24, 6, actor_hi=ah())
         if rng.random() < 0.3:
             vv[rng.randrange(R)] = 0
@@ -322,6 +335,18 @@ def test_fold_panic_parity_per_doc(eng, mode):
             se, svv = random_state(rng, R, rng.randint(0, 8), 24, 6, actor_hi=ah())
             t = random_state(rng, R, rng.randint(0, 3), 24, 6, actor_hi=ah())[0] if delta else []
             chain.append((rng.randrange(R + 1) if rng.random() < 0.1 else rng.randrange(R), svv, se, t))
+        yield e, vv, chain
+
+
+@pytest.mark.parametrize("mode", [CRDT_FOLD_AWSET, CRDT_FOLD_DELTA])
+def test_fold_panic_parity_per_doc(eng, mode):
+    """actor == len(VV) panics exactly where the reference evaluates HasDot on
+    it (a full step's add check, a tombstone's check, a gap step's removal
+    check, the path select), and actor > len(VV) is "never seen": one
+    document per call, the oracle's verdict against the kernel's."""
+    R = PANIC_R
+    seen_err = seen_ok = 0
+    for e, vv, chain in panic_cases(mode):
         dst, srcs = batch_of(R, [(e, vv)]), src_batch_of(R, [chain])
         rc, want = oracle.fold(mode, dst, srcs)
         if rc != 0:
@@ -335,21 +360,24 @@ def test_fold_panic_parity_per_doc(eng, mode):
     assert seen_err > 10 and seen_ok > 10
 
 
+# dst has seen actor 1 up to 5: src (actor 1) entries covered, no tombstones -> no-op, VV untouched
+NOOP_FC_DST = [([(1, 0, 1)], [1, 5]), ([(1, 0, 1)], [1, 0]), ([(1, 0, 1), (2, 1, 1)], [1, 5])]
+NOOP_FC_SRCS = [[(1, [9, 5], [(3, 1, 4)], [])],              # no-op
+                [(1, [9, 5], [(3, 1, 4)], [(1, 0, 9)])],     # first contact: tombstone ignored, (A 1) removed (9>=1)
+                [(1, [1, 6], [(3, 1, 6)], [(2, 1, 6)])]]     # delta: add (B 6), tombstone removes key 2
+NOOP_FC_WANT = [([(1, 0, 1)], [1, 5]), ([(3, 1, 4)], [9, 5]), ([(1, 0, 1), (3, 1, 6)], [1, 6])]
+
+
 def test_delta_fold_noop_and_first_contact(eng):
     R = 2
-    # dst has seen actor 1 up to 5: src (actor 1) entries covered, no tombstones -> no-op, VV untouched
-    dst = batch_of(R, [([(1, 0, 1)], [1, 5]), ([(1, 0, 1)], [1, 0]), ([(1, 0, 1), (2, 1, 1)], [1, 5])])
-    per = [[(1, [9, 5], [(3, 1, 4)], [])],              # no-op
-           [(1, [9, 5], [(3, 1, 4)], [(1, 0, 9)])],     # first contact: tombstone ignored, (A 1) removed (9>=1)
-           [(1, [1, 6], [(3, 1, 6)], [(2, 1, 6)])]]     # delta: add (B 6), tombstone removes key 2
-    srcs = src_batch_of(R, per)
+    dst = batch_of(R, NOOP_FC_DST)
+    srcs = src_batch_of(R, NOOP_FC_SRCS)
     rc, want = oracle.fold(CRDT_FOLD_DELTA, dst, srcs)
     assert rc == 0
     got = eng.fold(CRDT_FOLD_DELTA, dst, srcs)
     assert_same(got, want, 3, R)
-    assert out_doc(got, 0, R) == ([(1, 0, 1)], [1, 5])
-    assert out_doc(got, 1, R) == ([(3, 1, 4)], [9, 5])
-    assert out_doc(got, 2, R) == ([(1, 0, 1), (3, 1, 6)], [1, 6])
+    for d in range(3):
+        assert out_doc(got, d, R) == NOOP_FC_WANT[d]
 
 
 def test_delta_fold_actor_range(eng):

@@ -100,9 +100,8 @@ def test_tile_boundaries_split_common_pairs(shaped, n):
     check_join_and_exchange(shaped, dst, src, R)
 
 
-def test_tile_equal_key_sets(shaped):
-    """Identical key sets: every dst element is followed by its src twin, so the
-    merge path cuts between twins at every odd tile boundary."""
+def equal_key_docs():
+    """(R, dst docs, src docs) with identical key sets on both sides."""
     rng = random.Random(5)
     R = 2
     docs_d, docs_s = [], []
@@ -110,14 +109,18 @@ def test_tile_equal_key_sets(shaped):
         keys = sorted(rng.sample(range(10 ** 9), n))
         docs_d.append(([(k, rng.randrange(2), rng.randint(1, 9)) for k in keys], [5, 5]))
         docs_s.append(([(k, rng.randrange(2), rng.randint(1, 9)) for k in keys], [4, 6]))
+    return R, docs_d, docs_s
+
+
+def test_tile_equal_key_sets(shaped):
+    """Identical key sets: every dst element is followed by its src twin, so the
+    merge path cuts between twins at every odd tile boundary."""
+    R, docs_d, docs_s = equal_key_docs()
     check_join_and_exchange(shaped, batch_of(R, docs_d), batch_of(R, docs_s), R)
 
 
-def test_tile_disjoint_key_ranges(shaped):
-    """Every dst key below every src key, and the reverse: the merge path runs
-    along one run and then the other, so each tile's split is as far as it gets
-    from the proportional guess the plan's galloping search starts from
-    (tile.hip, merge_path_gallop)."""
+def disjoint_key_docs():
+    """(R, dst docs, src docs): every dst key below every src key, and the reverse."""
     rng = random.Random(11)
     R = 2
     docs_d, docs_s = [], []
@@ -128,6 +131,15 @@ def test_tile_disjoint_key_ranges(shaped):
         flip = len(docs_d) % 2 == 1
         docs_d.append((ent(hi if flip else lo), [5, 5]))
         docs_s.append((ent(lo if flip else hi), [4, 6]))
+    return R, docs_d, docs_s
+
+
+def test_tile_disjoint_key_ranges(shaped):
+    """Every dst key below every src key, and the reverse: the merge path runs
+    along one run and then the other, so each tile's split is as far as it gets
+    from the proportional guess the plan's galloping search starts from
+    (tile.hip, merge_path_gallop)."""
+    R, docs_d, docs_s = disjoint_key_docs()
     check_join_and_exchange(shaped, batch_of(R, docs_d), batch_of(R, docs_s), R)
 
 
