@@ -23,161 +23,21 @@
 
 namespace crdt {
 
-// ---- build options (tools/fold_probe.hip timing builds override them) ----
-// Measured on config 3 / 5 with timing builds, three interleaved rounds each,
-// outputs checksummed equal (round 4):
-//  * CRDT_FOLD_PAD_VALU / _SALU = 200 (diagnostic: 200 dependent VALU or SALU
-//    instructions per document): +8 % / +7 % on config 3, +20 % / +26 % on
-//    config 5 -- config 5 (6 waves per SIMD) is near issue-bound, config 3
-//    (4 waves per SIMD) is bound by its per-document dependent chain;
-//  * CRDT_FOLD_PURE_CHUNKS (buffer loads for a chunk inside one region instead
-//    of per-lane pointer selects): no change (-0.5 % / +1 %), off;
-//  * branch-free slot walks (every lane issues the atomics and reads, no
-//    per-lane branch): +8 % / +5 %, dropped; branch-free staging (below): -2 %
-//    on config 5, kept;
-//  * CRDT_FOLD_LDS_PAD (diagnostic: LDS padding, fewer waves per CU): config 3
-//    16 -> 14 -> 12 waves per CU costs +9 % / +35 %, config 5 24 -> 22 -> 16
-//    costs +9 % / +18 % -- both folds scale with resident waves, i.e. they are
-//    bound by each document's dependent chain, not by bytes or issue;
-//  * more waves by squeezing registers: the lean delta pass at 5 waves per SIMD
-//    (95 VGPRs, 40 spilled) +59 %, the lean AWSet pass at 7 (72 VGPRs) +13 %;
-//    counters and clocks staged as u32 (half the LDS of tc / vs / svv, the
-//    documents with a word >= 2^32 deferred) +2.5 % at the same occupancy;
-//    dropped;
-//  * the lean passes defer > 15 sources before their prefetch and keep no
-//    registers for words they never load (the second offset chunk, the lean
-//    AWSet pass's second clock chunk): config 5 -1.5 %, kept; the lean AWSet
-//    pass then fits 7 waves per SIMD in 72 VGPRs (3 spilled): another -0.5 %,
-//    within noise, not taken;
-//  * the lean delta pass's survivors written per slot quad inside the walk (no
-//    Emit registers) with u32 staging: 128 -> 109 VGPRs, but +7.5 % at 4 waves
-//    per SIMD, and at 5 waves (96 VGPRs, 3 spilled) still +5.6 % on config 3
-//    (+3 % config 5); dropped;
-//  * tombstone check by reading a short source's <= 8 entries at once instead
-//    of binary-search probes: +8 % on config 3 (one VGPR spills); the source
-//    actors kept in a register instead of re-read from LDS: no change; dropped;
-//  * CRDT_FOLD_NOFULL_PASS: a delta document with no full step (every step a
-//    delta) walks its slots once -- the entry/add/drop time words and the last
-//    entry row in one pass, one wave barrier fewer in the chain: config 3
-//    1.87 -> 1.81 ms (-3.7 %), config 5 unchanged, on (profiles/r04y_*);
-//  * the per-step "has a changed entry / an effective tombstone" flags OR-ed
-//    over the wave with DPP instead of written to LDS and read back: no change
-//    (within 0.3 %), kept as the simpler form;
-//  * tuple loads by region (one descriptor per region and array, the regions'
-//    zero-filled out-of-range loads OR-ed): +30 % on both -- three times the
-//    load instructions of a straddling chunk, plus spills; dropped.  HasDot of
-//    every source tuple computed in the classify pass (the walk then reads no
-//    clocks): +0.5 %, dropped.  8 more (out-of-range) store instructions per
-//    document: +0.7 % config 3, +7 % config 5 -- config 3 is not bound by its
-//    memory-instruction count;
-//  * CRDT_FOLD_STAGE_STORES 2 (survivors staged by slot in LDS, then 16-byte
-//    stores: 5 store instructions a document instead of 12; the range check
-//    drops each dword past the last survivor, tools/buf_probe):
-//    -1.8 % config 3, +2.5 % config 5 (profiles/r04z_fold_variants.log), off;
-//  * CRDT_FOLD_PTAB (the prefetch reads its region's base pointers from a
-//    12-entry LDS table instead of a 3-way select of scalar pointers: 330
-//    fewer static VALU in the lean delta kernel): -1.8 % config 3, +0.9 %
-//    config 5; on for the delta folds only;
-//  * CRDT_FOLD_IDX32 (the AWSet prefetch selects 32-bit slot indices and knows
-//    it has no tombstone region: no exec-masked 64-bit arithmetic; -74 static
-//    VALU, -33 SALU): config 5 -3 % (noisy), on;
-//  * CRDT_FOLD_CLASSIFY_UNIFORM (chunk-uniform guards + predicated per-lane
-//    entry / tombstone checks in the delta classify, -80 static SALU): +1.3 %
-//    on config 3, off.  PMC of the lean delta pass at HEAD: 691 VALU, 485 SALU,
-//    97 LDS instructions a document (round 3: 837 / 533 / 104;
-//    profiles/r04c3_pmc_summary.txt);
-//  * documents per wave (CRDT_FOLD_K_DELTA / CRDT_FOLD_K) 8 / 16 and 24 / 48
-//    against 16 / 32: equal or slower on both configs, 16 / 32 kept (round 4);
-//    with the fused delta walk (round 6, profiles/r06zj_fold_docs_per_wave.log,
-//    three interleaved rounds each): delta 8 and 6 -1.3-1.9 %, 4 +1.2 %, 12
-//    -0.4 % against 16 -- 8 kept; AWSet 16 / 24 against 32 within noise, 32 kept.
-// 1: survivors staged through LDS and written as contiguous lines -- measured
-// 4 % slower on config 3 and 5 % on config 5 (tools/fold_probe.hip timing
-// builds, three interleaved rounds), so off: each lane stores its own
-// survivors at their slots.  (CRDT_FOLD_NO_STORES, a diagnostic bound that
-// writes nothing, is only 4 % faster: the folds are not bound by their stores.)
-#ifndef CRDT_FOLD_STAGE_STORES
-#define CRDT_FOLD_STAGE_STORES 0
-#endif
-#ifndef CRDT_FOLD_NO_STORES
-#define CRDT_FOLD_NO_STORES 0
-#endif
-// diagnostic bounds (timing builds only): no per-document fold / no loads after the first document
-#ifndef CRDT_FOLD_DIAG_NOCOMPUTE
-#define CRDT_FOLD_DIAG_NOCOMPUTE 0
-#endif
-#ifndef CRDT_FOLD_DIAG_NOLOAD
-#define CRDT_FOLD_DIAG_NOLOAD 0
-#endif
-#ifndef CRDT_FOLD_DIAG_SKIP_CLASSIFY  // diagnostic: no classify pass (keys read, nothing kept but the document)
-#define CRDT_FOLD_DIAG_SKIP_CLASSIFY 0
-#endif
-#ifndef CRDT_FOLD_DIAG_SKIP_WALK  // diagnostic: no slot walk (nothing written)
-#define CRDT_FOLD_DIAG_SKIP_WALK 0
-#endif
-// CRDT_FOLD_PAD_STORES (with CRDT_FOLD_STAGE_STORES 1, diagnostic): each array's
-// staged stores run on to the end of the last survivor's cache line, within
-// the document's output capacity (slack past the live count is unspecified),
-// so no output line is written partially.
-#ifndef CRDT_FOLD_PAD_STORES
-#define CRDT_FOLD_PAD_STORES 0
-#endif
-#ifndef CRDT_FOLD_PURE_CHUNKS
-#define CRDT_FOLD_PURE_CHUNKS 0
-#endif
-#ifndef CRDT_FOLD_AWSET_ONE_ROUND
-#define CRDT_FOLD_AWSET_ONE_ROUND 1
-#endif
-#ifndef CRDT_FOLD_CLASSIFY_UNIFORM
-#define CRDT_FOLD_CLASSIFY_UNIFORM 0
-#endif
-#ifndef CRDT_FOLD_IDX32
-#define CRDT_FOLD_IDX32 1
-#endif
-#ifndef CRDT_FOLD_PTAB
-#define CRDT_FOLD_PTAB 1
-#endif
-#ifndef CRDT_FOLD_NOFULL_PASS
-#define CRDT_FOLD_NOFULL_PASS 1
-#endif
-#ifndef CRDT_FOLD_LDS_PAD
-#define CRDT_FOLD_LDS_PAD 0
-#endif
-// CRDT_FOLD_GLOBAL_PTAB: the PTAB prefetch's tuple loads through global-address-
-// space pointers (global_load) instead of generic ones (flat_load, which also
-// counts in lgkmcnt: every LDS wait of the fold then waited for the prefetch).
-#ifndef CRDT_FOLD_GLOBAL_PTAB
-#define CRDT_FOLD_GLOBAL_PTAB 1
-#endif
-// CRDT_FOLD_TOMB_TAB: the delta classify's "re-added in the same source" check
-// (awset-delta_test.go:93-102) through a per-low-key-byte step bitmap, searching
-// the source's entries only on a possible hit (see the classify pass).
-#ifndef CRDT_FOLD_TOMB_TAB
-#define CRDT_FOLD_TOMB_TAB 1
-#endif
-// CRDT_FOLD_FUSED: the lean delta pass's documents with no full step classified
-// and walked in one pass (fused_delta_walk)
-#ifndef CRDT_FOLD_LIST_SPREAD
-#define CRDT_FOLD_LIST_SPREAD 1  // 0: the deferred list in runs of K (A/B builds)
-#endif
+// ---- build constants ---------------------------------------------------------
+// What a build may still set (tools/fold_probe.hip timing builds, library
+// variants): the documents per wave and waves per workgroup CRDT_FOLD_K,
+// CRDT_FOLD_K_DELTA, CRDT_FOLD_WAVES, CRDT_FOLD_WAVES_DELTA; the waves per SIMD
+// CRDT_FOLD_DELTA_WPE, CRDT_FOLD_AWSET_WPE, CRDT_FOLD_LEAN_WPE,
+// CRDT_FOLD_AWSET_LEAN_WPE (each defined where it is used, below); the lean
+// passes' document order CRDT_FOLD_XCD_MAP; and CRDT_STAMPS (phase stamps).
+// The alternatives and diagnostic bounds measured and retired on the way here
+// are recorded in DESIGN.md, "Fold: build options tried and retired".
 #ifndef CRDT_FOLD_XCD_MAP
 #define CRDT_FOLD_XCD_MAP 1  // XCD-contiguous document ranges: 0 none, 1 AWSet lean pass, 2 both lean passes
-#endif
-#ifndef CRDT_FOLD_FUSED
-#define CRDT_FOLD_FUSED 1
 #endif
 // pointer to global (address space 1) memory
 template <typename T>
 using gptr = const T __attribute__((address_space(1)))*;
-#ifndef CRDT_FOLD_PAD_VALU
-#define CRDT_FOLD_PAD_VALU 0
-#endif
-#ifndef CRDT_FOLD_PAD_SALU
-#define CRDT_FOLD_PAD_SALU 0
-#endif
-#ifndef CRDT_FOLD_PAD_VMEM
-#define CRDT_FOLD_PAD_VMEM 0
-#endif
 
 // ---- the fold restated per key ---------------------------------------------
 // A key's fate over the whole fold depends only on its own tuples (its dot in
@@ -260,13 +120,10 @@ struct alignas(16) FoldSmem {
     // 8-byte aligned: the AWSet walk keeps 64-bit slot masks here, updated
     // with 64-bit LDS atomics, which fault on a misaligned address
     alignas(16) uint16_t stag[NCAP];  // kept tuples' tags
-    uint8_t anye[MCAP];              // the prefetch's per-region base table (CRDT_FOLD_PTAB: 12 x 8 bytes
-    uint8_t anyt[MCAP];              //  over both; dead during a fold, whose walk tables reach over them)
+    uint8_t anye[MCAP];              // the delta prefetch's per-region base table (12 x 8 bytes over
+    uint8_t anyt[MCAP];              //  both; dead during a fold, whose walk tables reach over them)
     alignas(4) uint8_t smark[NCAP];  // s + 1 where source s's entries / tombstones end (step of a tuple)
     alignas(8) uint16_t dbase[256];  // dense_sort: first sorted position of each key slot (64-bit stores)
-#if CRDT_FOLD_LDS_PAD
-    uint8_t pad[CRDT_FOLD_LDS_PAD];  // diagnostic builds: fewer waves per CU by LDS (occupancy slope)
-#endif
 };
 
 // The members reached by 64-bit LDS accesses (atomics on stag, stores on
@@ -681,7 +538,7 @@ __device__ __forceinline__ bool dense_delta_walk(Smem& m, const uint64_t (&key)[
     // kept entry adds and no gap can drop it, so the entry-time pass is not
     // needed -- the slot's last entry is an atomic max of (time << 8 | tuple)
     // in erows' words, in the same pass as the add and drop bits.
-    const bool nofull = CRDT_FOLD_NOFULL_PASS && full_mask == 0ull;
+    const bool nofull = full_mask == 0ull;
     if (nofull) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1096,18 +953,14 @@ constexpr int fold_waves() { return DELTA ? kFoldWavesD : kFoldWaves; }
 constexpr int kFoldStoreAux = kAuxNT;
 constexpr int kFoldK = CRDT_FOLD_K;  // consecutive documents per wavefront (AWSet folds)
 constexpr int kFoldKD = CRDT_FOLD_K_DELTA;  // (delta folds: 8; 16 was 2 % faster than 32, 8 1.3-1.9 % than 16)
-// stores of one document's write-out: walk rounds x 3 + count + VV
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // lane E of (hi:lo) := the wave-uniform x (v_writelane: no select, no exec change)
 template <int E>
 __device__ __forceinline__ void lane_put(uint32_t& lo, uint32_t& hi, uint64_t x) {
     asm("v_writelane_b32 %0, %1, %2" : "+v"(lo) : "s"((uint32_t)x), "i"(E));
     asm("v_writelane_b32 %0, %1, %2" : "+v"(hi) : "s"((uint32_t)(x >> 32)), "i"(E));
 }
-// (CRDT_FOLD_STAGE_STORES 2: 16-byte stores, two keys / counters or four actors a lane)
-__host__ __device__ constexpr int fold_stores(int nch) {
-    return CRDT_FOLD_STAGE_STORES == 2 ? 2 * ((nch + 1) / 2) + (nch + 3) / 4 + 2 : nch * 3 + 2;
-}
+// stores of one document's write-out: walk rounds x 3 + count + VV
+__host__ __device__ constexpr int fold_stores(int nch) { return nch * 3 + 2; }
 
 template <int K, bool DELTA, bool LEAN, bool LIST>
 __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_waves_per_eu(FoldShape<DELTA, LEAN>::WPE))) void fold_pipe_kernel(BatchView dst, SrcView sb, OutView out, Work wk) {
@@ -1118,7 +971,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
     // dense_awset_walk (slots < 64: one round; a document it cannot walk is
     // deferred, nothing written), so its second round would be all out of
     // range -- not issued (config 5: 3 fewer store instructions a document)
-    constexpr int WQ = (LEAN && !DELTA && CRDT_FOLD_AWSET_ONE_ROUND) ? 1 : NCH;
+    constexpr int WQ = (LEAN && !DELTA) ? 1 : NCH;
     using Smem = FoldSmem<FoldShape<DELTA, LEAN>::VCAP, 64 * NCH>;
     static_assert(fold_smem_aligned<FoldShape<DELTA, LEAN>::VCAP, 64 * NCH>(),
                   "FoldSmem: a 64-bit LDS access target is not 8-byte aligned");
@@ -1143,7 +996,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                                       n_docs)
                                 : n_docs;
     uint32_t kr = (uint32_t)K;
-    if constexpr (LIST && DELTA && CRDT_FOLD_LIST_SPREAD) {
+    if constexpr (LIST && DELTA) {
         const uint32_t waves = gridDim.x * (uint32_t)fold_waves<DELTA>();
         kr = uniform(max(1u, min((uint32_t)K, (n_run + waves - 1u) / waves)));
     }
@@ -1244,7 +1097,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
     auto prefetch = [&](FoldPref<NCH, VCH>& P, const DocMeta& q) {
         // (delta folds only: -1.8 % on config 3; the AWSet folds select between
         // two regions, +0.9 % on config 5 -- profiles/r04z_fold_variants.log)
-        if constexpr (DELTA && CRDT_FOLD_PTAB) {
+        if constexpr (DELTA) {
         // Per-region base table in LDS (the 128 spare bytes at anye / anyt,
         // dead here): entry r * 4 + {0 keys, 1 counters, 2 actors} points at
         // tuple 0 of the document's index space in region r's array, so a lane
@@ -1261,11 +1114,9 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             lane_put<4>(lo, hi, reinterpret_cast<uint64_t>(sb.keys) + 8u * en);
             lane_put<5>(lo, hi, reinterpret_cast<uint64_t>(sb.counters) + 8u * en);
             lane_put<6>(lo, hi, reinterpret_cast<uint64_t>(sb.actors) + 4u * en);
-            if (DELTA) {
-                lane_put<8>(lo, hi, reinterpret_cast<uint64_t>(sb.tkeys) + 8u * tn);
-                lane_put<9>(lo, hi, reinterpret_cast<uint64_t>(sb.tcounters) + 8u * tn);
-                lane_put<10>(lo, hi, reinterpret_cast<uint64_t>(sb.tactors) + 4u * tn);
-            }
+            lane_put<8>(lo, hi, reinterpret_cast<uint64_t>(sb.tkeys) + 8u * tn);
+            lane_put<9>(lo, hi, reinterpret_cast<uint64_t>(sb.tcounters) + 8u * tn);
+            lane_put<10>(lo, hi, reinterpret_cast<uint64_t>(sb.tactors) + 4u * tn);
             if (lane < 12) ptab[lane] = ((uint64_t)hi << 32) | lo;
             wave_sync();
         }
@@ -1278,7 +1129,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                 i = i < q.N ? i : q.N - 1u;
                 const uint32_t r4 = (i >= q.n ? 4u : 0u) + (i >= nE ? 4u : 0u);
                 const uint64_t kb = ptab[r4], cb = ptab[r4 + 1], ab = ptab[r4 + 2];
-#if CRDT_FOLD_GLOBAL_PTAB
                 // Global (not generic) loads: a FLAT load also counts in lgkmcnt, so
                 // every LDS wait of the current document's fold -- the first comes
                 // right after this prefetch -- would wait for the next document's
@@ -1286,49 +1136,22 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                 P.k[c] = __builtin_nontemporal_load(reinterpret_cast<gptr<uint64_t>>(kb) + i);
                 P.a[c] = __builtin_nontemporal_load(reinterpret_cast<gptr<uint32_t>>(ab) + i);
                 P.c[c] = __builtin_nontemporal_load(reinterpret_cast<gptr<uint64_t>>(cb) + i);
-#else
-                P.k[c] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(kb) + i);
-                P.a[c] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(ab) + i);
-                P.c[c] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(cb) + i);
-#endif
             }
         }
         } else {
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-#if CRDT_FOLD_PURE_CHUNKS
-            // a chunk inside one region (the document's entries, the source
-            // entries or the tombstones): buffer loads from that region's
-            // scalar base, no per-lane pointer select
-            const uint32_t lo = c * 64u, hi = lo + 64u;
-            const bool pure_d = hi <= q.n, pure_e = lo >= q.n && hi <= q.n + q.E;
-            if (lo < q.N && (pure_d || pure_e)) {
-                const uint32_t r0 = pure_d ? q.doff + lo : q.e0 + (lo - q.n);
-                const uint32_t o8 = lane * 8u, o4 = lane * 4u;
-                const rsrc_t rk = make_rsrc(pure_d ? dst.keys + r0 : sb.keys + r0, 512u);
-                const rsrc_t ra = make_rsrc(pure_d ? dst.actors + r0 : sb.actors + r0, 256u);
-                const rsrc_t rc = make_rsrc(pure_d ? dst.counters + r0 : sb.counters + r0, 512u);
-                P.k[c] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(rk, (int)o8, 0, kAuxNT));
-                P.a[c] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(ra, (int)o4, 0, kAuxNT);
-                P.c[c] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(rc, (int)o8, 0, kAuxNT));
-            } else
-#endif
             if ((uint32_t)c * 64u < q.N) {
                 uint32_t i = c * 64u + lane;
                 i = i < q.N ? i : q.N - 1u;
-#if CRDT_FOLD_IDX32
-                // 32-bit index selects (slot indices are u32), no tombstone region
-                // in an AWSet fold: no exec-masked 64-bit arithmetic per region
-                const bool isd = i < q.n, iss = !DELTA || i < q.n + q.E;
-                const size_t idx = isd ? q.doff + i : (iss ? q.e0 + (i - q.n) : q.t0 + (i - q.n - q.E));
-#else
-                const bool isd = i < q.n, iss = i < q.n + q.E;
-                const size_t idx = isd ? (size_t)q.doff + i
-                                       : (iss ? (size_t)q.e0 + (i - q.n) : (size_t)q.t0 + (i - q.n - q.E));
-#endif
-                const uint64_t* kb = isd ? dst.keys : (iss ? sb.keys : sb.tkeys);
-                const uint32_t* ab = isd ? dst.actors : (iss ? sb.actors : sb.tactors);
-                const uint64_t* cb = isd ? dst.counters : (iss ? sb.counters : sb.tcounters);
+                // An AWSet fold has no tombstone region: one select between the
+                // document and the source entries, on 32-bit indices (slot indices
+                // are u32) -- no exec-masked 64-bit arithmetic per region
+                const bool isd = i < q.n;
+                const size_t idx = isd ? q.doff + i : q.e0 + (i - q.n);
+                const uint64_t* kb = isd ? dst.keys : sb.keys;
+                const uint32_t* ab = isd ? dst.actors : sb.actors;
+                const uint64_t* cb = isd ? dst.counters : sb.counters;
                 // non-temporal: every tuple is read once (0.5 % faster, measured)
                 P.k[c] = __builtin_nontemporal_load(kb + idx);
                 P.a[c] = __builtin_nontemporal_load(ab + idx);
@@ -1383,17 +1206,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
         if constexpr (!LEAN) asm volatile("" ::"v"(P.eo2));  // (the lean passes defer > 15 sources)
         if constexpr (DELTA) asm volatile("" ::"v"(P.to));
         if constexpr (DELTA && !LEAN) asm volatile("" ::"v"(P.to2));
-#if CRDT_FOLD_PAD_VALU || CRDT_FOLD_PAD_SALU
-        {   // diagnostic (tools/fold_probe timing builds): N dependent VALU / SALU
-            // instructions per document -- the slope says which issue port binds
-            uint32_t pv = lane, ps = k;
-#pragma unroll
-            for (int i = 0; i < CRDT_FOLD_PAD_VALU; ++i) asm volatile("v_add_u32 %0, %0, 1" : "+v"(pv));
-#pragma unroll
-            for (int i = 0; i < CRDT_FOLD_PAD_SALU; ++i) asm volatile("s_add_u32 %0, %0, 1" : "+s"(ps));
-            err |= (pv == 0xFFFFFFFFu && ps == 0xFFFFFFFFu) ? kErrWorkspace : 0u;
-        }
-#endif
         // ---- stage document k (its loads were issued one document ago)
         uint64_t vreg = 0;              // lane r < R: V_0[r]
         uint32_t soffv = 0, toffv = 0;  // lane s: end of source s's entries / tombstones
@@ -1421,9 +1233,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                     if ((uint32_t)c * 64u < msR && i < msR) m.svv[i] = P.sv[c];
                 }
             }
-            // (CRDT_FOLD_DIAG_NOLOAD: the offsets held are the run's first document's)
-            const uint32_t e0 = CRDT_FOLD_DIAG_NOLOAD ? rl(P.eo, 0) : cur.e0;
-            const uint32_t t0 = CRDT_FOLD_DIAG_NOLOAD ? rl(P.to, 0) : cur.t0;
+            const uint32_t e0 = cur.e0, t0 = cur.t0;
             const uint32_t nso = from_next_lane(LEAN ? 0u : rl(P.eo2, 0), P.eo);
             soffv = nso - e0;
             // per-source words of every lane (MCAP = 64: lanes past ms write words no step reads)
@@ -1449,9 +1259,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
         wave_sync();
         STAMP(0)
         // ---- issue document k+1's loads; they fly while document k is folded
-        // (CRDT_FOLD_DIAG_NOLOAD, diagnostic: none -- every document of the run folds
-        // the first one's tuples, which in configs 3 and 5 have the same shape)
-        if (k + 1 < cnt && !CRDT_FOLD_DIAG_NOLOAD) {
+        if (k + 1 < cnt) {
             const DocMeta nxt = meta(k + 1);
             STAMP(12)
             if (!nxt.big) prefetch(P, nxt);
@@ -1463,26 +1271,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
         uint32_t U = 0;  // survivors
         bool deferred = false;  // LEAN: the document is left to the general kernel
         Emit<NCH> em;
-#if CRDT_FOLD_DIAG_NOCOMPUTE
-        // diagnostic bound (tools/fold_probe timing builds): no fold at all -- the
-        // document's own entries written back as its survivors (memory traffic and
-        // the pipeline, without the per-document chain)
         if (!cur.big) {
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-                const uint32_t i = q * 64u + lane;
-                em.k[q] = m.tk[i];
-                em.a[q] = m.ta[i];
-                em.c[q] = m.tc[i];
-                em.off[q] = i < cur.n ? i : kOOB;
-            }
-            U = cur.n;
-            vfin = vreg;
-        }
-        if (false) {
-#else
-        if (!cur.big) {
-#endif
             const uint32_t n = cur.n, E = cur.E, N = cur.N, ms = cur.ms;
             // schedule: U_j, one lane per actor
             uint64_t v = vreg;
@@ -1554,7 +1343,7 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             STAMP(10)
             // (the fused pass searches a source's entries only on a table hit, rare:
             // it probes every level instead, and the scan below is skipped)
-            constexpr bool kFused = DELTA && LEAN && NCH == 4 && CRDT_FOLD_FUSED;
+            constexpr bool kFused = DELTA && LEAN && NCH == 4;
             uint32_t cmax = kFused ? 256u : 0u;  // longest source: depth of the re-add search
             if (DELTA && cur.X && !kFused) {
                 const uint32_t prv = dpp<0x138>(0u, soffv);  // wave_shr:1
@@ -1568,9 +1357,9 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                 cmax = (uint32_t)__builtin_amdgcn_readlane((int)cmax, 63);  // ... whose last lane has the maximum
             }
             STAMP(11)
-            // CRDT_FOLD_FUSED: the lean delta pass's common case, classify and slot
-            // walk in one pass (fused_delta_walk); 0: the two-pass form below
-            // The lean delta pass then holds nothing else: a document the fused pass
+            // The lean delta pass's common case, classify and slot walk in one pass
+            // (fused_delta_walk; the other kernels take the two-pass form below).
+            // The lean delta pass holds nothing else: a document the fused pass
             // does not take (a full step, a no-op step, > 15 sources, a key span of
             // 256 or more, an actor == len(VV)) is left to the general kernel.
             if constexpr (kFused) {
@@ -1585,12 +1374,14 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                 }
             }
             if constexpr (!kFused) {
-            // CRDT_FOLD_TOMB_TAB: est[key & 255] = the steps (< 32) with an entry of that
-            // low key byte, so a tombstone whose step bit is clear was not re-added in
-            // its source (effective) without the binary search below; a set bit (the
+            // The delta classify's "re-added in the same source" check
+            // (awset-delta_test.go:93-102) goes through a step bitmap per low key
+            // byte: est[key & 255] = the steps (< 32) with an entry of that low key
+            // byte, so a tombstone whose step bit is clear was not re-added in its
+            // source (effective) without the binary search below; a set bit (the
             // key, or another one with the same low byte) still searches.  Scratch:
             // stag onwards, dead until the keep phase / the walk.
-            const bool tab = CRDT_FOLD_TOMB_TAB && DELTA && cur.X != 0 && ms <= 32;
+            const bool tab = DELTA && cur.X != 0 && ms <= 32;
             uint32_t* est = reinterpret_cast<uint32_t*>(m.stag);
             static_assert(offsetof(Smem, dbase) + sizeof(m.dbase) - offsetof(Smem, stag) >= 1024,
                           "fold: step table space");
@@ -1604,10 +1395,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 key[c] = 0;
-                if (CRDT_FOLD_DIAG_SKIP_CLASSIFY && (uint32_t)c < NQ) {  // diagnostic: keys only
-                    key[c] = m.tk[c * 64u + lane < N ? c * 64u + lane : 0u];
-                    continue;
-                }
                 if ((uint32_t)c < NQ) {
                     const uint32_t i = c * 64u + lane;
                     const uint32_t ii = i < N ? i : 0u;
@@ -1616,41 +1403,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                     const uint64_t cc = m.tc[ii];
                     const uint32_t j = step[c] & 63u;
                     bool f = false;
-#if CRDT_FOLD_CLASSIFY_UNIFORM
-                    // Wave-uniform guards (does the chunk hold entries / tombstones)
-                    // and predicated per-lane work: no exec-mask regions per chunk.
-                    const uint32_t c64 = c * 64u;
-                    if (DELTA && c64 < n + E && c64 + 64u > n) {
-                        // MakeDeltaMergeData (:84-92): dst's clock has not seen the entry
-                        const bool ce = isE[c] && !((full_mask >> j) & 1ull);
-                        perr |= (ce && a == R) ? kErrActorRange : 0u;
-                        const bool cov = a < R;
-                        const uint64_t vj = issued(m.vs[j * R + (cov ? a : 0u)]);
-                        const bool fe = ce && !(cov && vj >= cc);
-                        me |= fe ? 1ull << j : 0ull;
-                        f = fe;
-                    }
-                    if (DELTA && c64 + 64u > n + E && c64 < N) {
-                        // effective: not re-added in the same source (:93-102); lanes
-                        // that are not tombstones search an empty range
-                        const uint32_t s0 = m.soff[j], lo = n + s0, len = isT[c] ? m.soff[j + 1] - s0 : 0u;
-                        uint32_t pos = 0;
-                        for (uint32_t st = 256; st > 0; st >>= 1) {
-                            if (st > cmax) continue;
-                            const bool in = pos + st <= len;
-                            const uint64_t v2 = issued(m.tk[in ? lo + pos + st - 1 : 0u]);
-                            pos += (in && v2 < key[c]) ? st : 0u;
-                        }
-                        const bool hit = pos < len;
-                        const uint32_t at = hit ? lo + pos : 0u;
-                        const uint64_t hk = issued(m.tk[at]), hc = issued(m.tc[at]);
-                        const uint32_t ha = issued(m.ta[at]);
-                        const bool in_s = hit && hk == key[c];
-                        const bool ft = isT[c] && !(in_s && (ha != a || hc > cc));
-                        mt |= ft ? 1ull << j : 0ull;
-                        f = f || ft;
-                    }
-#else
                     if (DELTA && isE[c] && !((full_mask >> j) & 1ull)) {
                         // MakeDeltaMergeData (:84-92): dst's clock has not seen the entry
                         if (a == R) perr |= kErrActorRange;
@@ -1677,7 +1429,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                         f = !(in_s && (m.ta[lo + pos] != a || m.tc[lo + pos] > cc));
                         mt |= f ? 1ull << j : 0ull;
                     }
-#endif
                     flag |= f ? (1u << c) : 0u;
                 }
             }
@@ -1690,7 +1441,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
                 const uint64_t anye = wave_or64(me);
                 tmask = wave_or64(mt) & low_mask(ms);
                 noop_mask = low_mask(ms) & ~full_mask & ~anye & ~tmask;
-                if (CRDT_FOLD_DIAG_SKIP_CLASSIFY) noop_mask = 0;  // (diagnostic: no replay either)
             }
             if (DELTA && noop_mask) {
                 // a step brings nothing: replay the schedule step by step with the exact clocks
@@ -1744,17 +1494,9 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             bool walked = false;
             if constexpr (!DELTA)
                 walked = dense_awset_walk<NCH>(m, key, step, N, n, ms, R, lane, lt, em, U, err);
-            else if constexpr (NCH == 4) {
-                if (CRDT_FOLD_DIAG_SKIP_WALK) {  // diagnostic: nothing resolved, nothing written
-                    walked = true;
-                    U = 0;
-#pragma unroll
-                    for (int q = 0; q < NCH; ++q) em.off[q] = kOOB, em.k[q] = key[q], em.a[q] = flag, em.c[q] = 0;
-                } else {
-                    walked = dense_delta_walk(m, key, step, isE, isT, flag, full_mask, noop_mask, N, n, ms, R, lane,
-                                              lt, em, U STAMP_ARGS);
-                }
-            }
+            else if constexpr (NCH == 4)
+                walked = dense_delta_walk(m, key, step, isE, isT, flag, full_mask, noop_mask, N, n, ms, R, lane, lt,
+                                          em, U STAMP_ARGS);
             if (LEAN && !walked) {  // left to the general kernel: nothing written here
                 deferred = true;
                 if (lane == 0) push_defer(wk, cur.d, n_docs);
@@ -1798,7 +1540,10 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             }  // !kFused
             STAMP(5)
         }
-        // ---- write the survivors (every store unconditional)
+        // ---- write the survivors (every store unconditional): each lane stores its
+        // own at their output slots (staged through LDS into whole lines first:
+        // slower, and a fold that writes nothing is only 4 % faster -- the folds
+        // are not bound by their stores)
         const uint32_t obase = cur.doff + cur.e0;
         const uint32_t capo = cur.big ? 0u : min(cur.slots + cur.E, (uint32_t)Smem::NCAP);
         const rsrc_t ok = make_rsrc(out.keys + obase, capo * 8u), oa = make_rsrc(out.actors + obase, capo * 4u),
@@ -1808,71 +1553,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             for (int q = 0; q < NCH; ++q) em.off[q] = kOOB;
             U = 0;
         }
-#if CRDT_FOLD_NO_STORES  // diagnostic bound (tools/fold_probe): the survivors are not written
-#pragma unroll
-        for (int q = 0; q < NCH; ++q) {
-            st64<kFoldStoreAux>(em.k[q], ok, kOOB);
-            st32<kFoldStoreAux>(em.a[q], oa, kOOB);
-            st64<kFoldStoreAux>(em.c[q], oc, kOOB);
-        }
-#elif CRDT_FOLD_STAGE_STORES
-        // The survivors are placed by output slot in LDS (tk / ta / tc are dead
-        // once the resolve is done), then each array is written lane l -> slot
-        // c * 64 + l: every store instruction covers contiguous whole lines.
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < NCH; ++q) {
-            const uint32_t o = em.off[q];
-            if (o != kOOB) {
-                m.tk[o] = em.k[q];
-                m.ta[o] = em.a[q];
-                m.tc[o] = em.c[q];
-            }
-        }
-        wave_sync();
-        if constexpr (CRDT_FOLD_STAGE_STORES == 2) {
-            // 16 bytes a lane: 128 keys / counters or 256 actors per store
-            // instruction (the descriptors end at the last survivor, and the
-            // range check drops each dword past it)
-            const rsrc_t sk = make_rsrc(out.keys + obase, min(U, capo) * 8u);
-            const rsrc_t sa = make_rsrc(out.actors + obase, min(U, capo) * 4u);
-            const rsrc_t sc = make_rsrc(out.counters + obase, min(U, capo) * 8u);
-#pragma unroll
-            for (int h = 0; h < (NCH + 1) / 2; ++h) {
-                const uint32_t i = h * 128u + 2u * lane;
-                const bool in = i < (uint32_t)Smem::NCAP;
-                const uint32_t ii = in ? i : 0u;
-                const u32x4 kv = *reinterpret_cast<const u32x4*>(&m.tk[ii]);
-                const u32x4 cv = *reinterpret_cast<const u32x4*>(&m.tc[ii]);
-                __builtin_amdgcn_raw_buffer_store_b128(kv, sk, (int)(in ? i * 8u : kOOB), 0, kFoldStoreAux);
-                __builtin_amdgcn_raw_buffer_store_b128(cv, sc, (int)(in ? i * 8u : kOOB), 0, kFoldStoreAux);
-            }
-#pragma unroll
-            for (int g = 0; g < (NCH + 3) / 4; ++g) {
-                const uint32_t i = g * 256u + 4u * lane;
-                const bool in = i < (uint32_t)Smem::NCAP;
-                const u32x4 av = *reinterpret_cast<const u32x4*>(&m.ta[in ? i : 0u]);
-                __builtin_amdgcn_raw_buffer_store_b128(av, sa, (int)(in ? i * 4u : kOOB), 0, kFoldStoreAux);
-            }
-        } else {
-            const uint32_t nw = min(U, capo);
-            uint32_t n8 = nw, n4 = nw;
-            if (CRDT_FOLD_PAD_STORES && nw != 0) {
-                n8 = min(((obase + nw + 15u) & ~15u) - obase, capo);
-                n4 = min(((obase + nw + 31u) & ~31u) - obase, capo);
-            }
-            const rsrc_t sk = make_rsrc(out.keys + obase, n8 * 8u);
-            const rsrc_t sa = make_rsrc(out.actors + obase, n4 * 4u);
-            const rsrc_t sc = make_rsrc(out.counters + obase, n8 * 8u);
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-                const uint32_t i = q * 64u + lane;
-                st64<kFoldStoreAux>(m.tk[i], sk, i * 8u);
-                st32<kFoldStoreAux>(m.ta[i], sa, i * 4u);
-                st64<kFoldStoreAux>(m.tc[i], sc, i * 8u);
-            }
-        }
-#else
 #pragma unroll
         for (int q = 0; q < WQ; ++q) {
             const uint32_t o = em.off[q];
@@ -1881,11 +1561,6 @@ __global__ __launch_bounds__(fold_waves<DELTA>() * 64) __attribute__((amdgpu_wav
             st32<kFoldStoreAux>(em.a[q], oa, o4);
             st64<kFoldStoreAux>(em.c[q], oc, o8);
         }
-#endif
-#if CRDT_FOLD_PAD_VMEM  // diagnostic: N more (all out-of-range) store instructions per document
-#pragma unroll
-        for (int i = 0; i < CRDT_FOLD_PAD_VMEM; ++i) st64<kFoldStoreAux>(em.k[0], ok, kOOB + 8u * i);
-#endif
         const uint32_t carry = U;
         const bool none = cur.big || deferred;
         st32(carry, make_rsrc(out.counts + cur.d, none ? 0u : 4u), lane == 0 ? 0u : kOOB);

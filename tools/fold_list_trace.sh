@@ -1,4 +1,4 @@
-# kernel trace of the fold passes (lean + deferred list) per library: bash tools/fold_list_trace.sh (GPU box; diagnostic)
+# kernel trace of the fold passes (lean + deferred list) per library: bash tools/fold_list_trace.sh (GPU box; diagnostic). Written for the looping-grid list pass A/B (a source change, dropped: profiles/r06zi_fold_list_grid_ab.log); it traces whatever libraries $LTLIBS names and depends on no fold build switch.
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for v in ${LTLIBS:-base}; do
   lib=go-crdt-playground_amd/crdtgpu/libcrdtgpu.so; [ "$v" = base ] || lib=tools/libcrdtgpu_$v.so

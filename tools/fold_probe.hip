@@ -6,6 +6,14 @@
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCRDT_STAMPS tools/fold_probe.hip -o tools/fold_probe
 //   tools/fold_probe [config 3|5] [docs]
+//
+// Without -DCRDT_STAMPS the same file is a timing build (tools/fold_time_NAME,
+// recipe ftime of tools/gpu_run.sh).  What -D may set in either: the fold's
+// constants CRDT_FOLD_K, CRDT_FOLD_K_DELTA, CRDT_FOLD_WAVES,
+// CRDT_FOLD_WAVES_DELTA, CRDT_FOLD_DELTA_WPE, CRDT_FOLD_AWSET_WPE,
+// CRDT_FOLD_LEAN_WPE, CRDT_FOLD_AWSET_LEAN_WPE and CRDT_FOLD_XCD_MAP (fold.hip),
+// and FOLD_SRC below.  FOLD_GENERAL in the environment runs the general kernel
+// over every document (no lean pass).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -22,8 +30,8 @@
 using namespace crdt;
 
 // order-independent checksum of an output (the live entries of every document,
-// their slot bounds, counts and clocks; slack slots are unspecified and some
-// variants write them): variants of the fold must print the same value
+// their slot bounds, counts and clocks; slack slots are unspecified, so they
+// are left out): variants of the fold must print the same value
 __global__ void checksum_kernel(const uint32_t* offsets, const uint32_t* counts, const uint64_t* vv, size_t n_vv,
                                 const uint64_t* keys, const uint32_t* actors, const uint64_t* ctrs, uint32_t n,
                                 unsigned long long* out) {

@@ -25,6 +25,8 @@
 #   ptest    pytest -m gpu on $PTEST (a -k expression)
 #   jab      config-2 exchange timed per library build ($JLIBS: base = the product library, X = tools/libcrdtgpu_X.so)
 #   ftime    fold timing builds tools/fold_time_$FTIME (space-separated variant names), interleaved, configs 3 and 5
+#            (tools/fold_probe.hip built with -D of the fold's constants: CRDT_FOLD_K, _K_DELTA, _WAVES, _WAVES_DELTA,
+#            _DELTA_WPE, _AWSET_WPE, _LEAN_WPE, _AWSET_LEAN_WPE, _XCD_MAP)
 #   tpass    config-4 exchange in passes of $TCAPS tiles vs one pass (tools/tile_passes.py)
 #   bench1   boundary_bench alone (C++ mirror ExchangeBatch, every document checked)
 #   lab      configs $LCONFIGS (default 3 5) timed by bench.py per library build ($LLIBS: base or X =
