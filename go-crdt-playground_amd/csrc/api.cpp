@@ -489,7 +489,7 @@ int crdt_ctx_set_option(crdt_ctx* ctx, const char* name, int64_t value) {
         ctx->probe_blocks_per_cu = (uint32_t)value;
         return CRDT_OK;
     }
-    if (!strcmp(name, "fold_lean_first")) {  // delta folds: slot-walk pass first, the rest deferred (fold.hip)
+    if (!strcmp(name, "fold_lean_first")) {  // both fold modes: lean slot-walk pass first, the rest deferred (fold.hip, launch_fold)
         ctx->fold_lean_first = value != 0;
         return CRDT_OK;
     }

@@ -256,6 +256,7 @@ __device__ __forceinline__ bool dense_sort(Smem& m, uint64_t (&k)[EPL], uint32_t
     // slot and step field are recomputed from k / t where needed (no extra
     // registers live across the sort: the AWSet fold runs at 128 VGPRs)
     const uint64_t bs = b - 0x80000000ull + uniform(lo);  // key of slot 0
+    if (bs + (hi - lo) < bs) return false;  // the keys wrap through 2^64: slot order is not key order
     static_assert(sizeof(m.tk) >= 1024, "dense_sort: tk holds the 256 slot masks");
     ev[lane] = 0u;
     ev[64 + lane] = 0u;
@@ -390,6 +391,7 @@ __device__ __forceinline__ bool dense_awset_walk(Smem& m, const uint64_t (&key)[
     hi = wave_minmax<true>(hi);
     if (hi - lo >= 64u) return false;
     const uint64_t kb = b - 0x80000000ull + lo;  // key of slot 0
+    if (kb + (hi - lo) < kb) return false;  // the keys wrap through 2^64: slot order is not key order
     uint32_t a[NCH], sl[NCH], row[NCH];
     uint64_t cc[NCH];
     bool anyR = false;
@@ -523,6 +525,7 @@ __device__ __forceinline__ bool dense_delta_walk(Smem& m, const uint64_t (&key)[
     hi = wave_minmax<true>(hi);
     if (lo > hi || hi - lo >= 256u) return false;  // lo > hi: nothing kept
     const uint64_t kb = b - 0x80000000ull + lo;   // key of slot 0
+    if (kb + (hi - lo) < kb) return false;         // the keys wrap through 2^64: slot order is not key order
     uint32_t* erows = reinterpret_cast<uint32_t*>(m.tk);  // [256] entry times of the slot
     uint32_t* addw = erows + 256;                          // [256] add times
     uint32_t* dropw = reinterpret_cast<uint32_t*>(m.stag);  // [256] drop times
@@ -690,6 +693,7 @@ __device__ __forceinline__ int fused_delta_walk(Smem& m, const uint32_t (&step)[
         hi = wave_minmax<true>(hi);
         if (hi - lo >= 256u) return 0;
         b = b - 0x80000000ull + lo;  // key of slot 0
+        if (b + (hi - lo) < b) return 0;  // the keys wrap through 2^64: slot order is not key order
 #pragma unroll
         for (int c = 0; c < 4; ++c) sl[c] = (uint32_t)(key[c] - b) & 255u;
     }

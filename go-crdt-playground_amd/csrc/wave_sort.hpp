@@ -160,8 +160,10 @@ __device__ __forceinline__ void wave_bitonic_packed(uint64_t (&v)[EPL], uint32_t
 // n are padding).  Keys are taken relative to the first pair's key b: when
 // every key lies in [b - 2^15, b + 2^15) the pair packs into 32 bits (offset
 // << 16 | tag), when within [b - 2^47, b + 2^47) into 64 bits, both
-// order-preserving; otherwise the 80-bit comparison runs.  Returns with the
-// pairs in element order and pads (key ~0, tag 0xFFFF) last.
+// order-preserving; otherwise the 80-bit comparison runs -- also when the keys
+// are that close only modulo 2^64 (some near 0, some near 2^64 - 1): their
+// offsets from b would sort them across the wrap.  Returns with the pairs in
+// element order and pads (key ~0, tag 0xFFFF) last.
 template <int EPL>
 __device__ __forceinline__ void wave_sort_pairs(uint64_t (&k)[EPL], uint32_t (&t)[EPL], uint32_t n, uint32_t lane) {
     const uint64_t b = readlane64(k[0], 0);
@@ -170,8 +172,9 @@ __device__ __forceinline__ void wave_sort_pairs(uint64_t (&k)[EPL], uint32_t (&t
     for (int q = 0; q < EPL; ++q) {
         const bool valid = lane * EPL + q < n;
         const uint64_t d = k[q] - b;
-        o16 |= valid && d + 0x8000ull >= 0x10000ull;
-        o48 |= valid && d + (1ull << 47) >= (1ull << 48);
+        const bool wrap = (k[q] < b) != ((int64_t)d < 0);  // the offset's sign is not the keys' order
+        o16 |= valid && (wrap || d + 0x8000ull >= 0x10000ull);
+        o48 |= valid && (wrap || d + (1ull << 47) >= (1ull << 48));
     }
     if (!ballot(o16)) {
         uint32_t v[EPL];

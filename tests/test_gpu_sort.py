@@ -88,6 +88,35 @@ def test_sort_key_widths_and_run_edges(eng, universe):
         assert e == b.doc(d)[0], (d, n)
 
 
+@pytest.mark.parametrize("reach", [20, 2 ** 14, 2 ** 40])
+def test_sort_keys_wrapping_through_2_64(eng, reach):
+    """Keys on both sides of the wrap -- a few below 2^64, a few above 0 -- lie within
+    `reach` of each other only modulo 2^64: the packed compare widths of the
+    in-register sort take keys by their offset from the first one, which would order
+    them across the wrap.  Every run size of the register path, the first key drawn
+    from either side."""
+    rng = random.Random(reach % 997)
+    nrng = np.random.default_rng(reach % 997)
+    R = 2
+    top = 2 ** 64
+    docs = []
+    for n in (2, 3, 17, 64, 65, 128, 129, 256):
+        for _ in range(4):
+            ks = set()
+            while len(ks) < n:
+                off = rng.randrange(max(reach, 2 * n))
+                ks.add(off if rng.random() < 0.5 else top - 1 - off)
+            ks |= {0, top - 1}
+            docs.append(([(k, rng.randint(0, R - 1), rng.randint(1, 50)) for k in sorted(ks)], [rng.randint(0, 50)] * R))
+    b = batch_of(R, docs)
+    got = eng.sort(shuffled(b, nrng))
+    for d in range(b.n_docs):
+        o, n = int(got.offsets[d]), int(got.counts[d])
+        assert n == b.live(d)
+        e = list(zip(got.keys[o:o + n].tolist(), got.actors[o:o + n].tolist(), got.counters[o:o + n].tolist()))
+        assert e == b.doc(d)[0], (d, n)
+
+
 @pytest.mark.parametrize("n", [40, 200, 3000])
 def test_sort_duplicate_in_each_path(eng, n):
     """A repeated key is found by the register path and the merge-path passes."""
