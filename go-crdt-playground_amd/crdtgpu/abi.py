@@ -38,6 +38,10 @@ CRDT_CMP_KEYS = 1
 CRDT_CMP_DOTS = 2
 CRDT_CMP_A_AHEAD = 4
 CRDT_CMP_B_AHEAD = 8
+CRDT_DIFF_REMOVED = 1
+CRDT_DIFF_ADDED = 2
+CRDT_DIFF_UPDATED = 4
+CRDT_DIFF_CLOCK = 8
 CRDT_DIG_ELEMENTS = 1
 CRDT_DIG_STATE = 2
 CRDT_OP_ADD = 0
@@ -109,6 +113,15 @@ class CQueryOut(ctypes.Structure):
 
 class CCompareOut(ctypes.Structure):
     _fields_ = [("flags", _vp), ("summary", _vp), ("worklist", _vp), ("n_work", _vp)]
+
+
+class CDiffOut(ctypes.Structure):
+    _fields_ = [
+        ("flags", _vp), ("summary", _vp),
+        ("rem_off", _vp), ("rem_keys", _vp), ("rem_actors", _vp), ("rem_counters", _vp),
+        ("ups_off", _vp), ("ups_keys", _vp), ("ups_actors", _vp), ("ups_counters", _vp),
+        ("ups_kind", _vp),
+    ]
 
 
 class CReplica(ctypes.Structure):
@@ -191,6 +204,8 @@ def signatures():
         "crdt_tomb_has_async": (ctypes.c_int, [_vp, P(CTombBatch), _u32, P(CQueryBatch), P(CQueryOut), _vp]),
         "crdt_awset_compare_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut), _vp]),
         "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
+        "crdt_awset_diff_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, _u32, P(CDiffOut), _vp]),
+        "crdt_awset_diff_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, _u32, P(CDiffOut)]),
         "crdt_awset_digest_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp]),
         "crdt_awset_digest_host": (ctypes.c_int, [P(CAWSetBatch), P(CTombBatch), _vp]),
         "crdt_digest_diff_async": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, P(CCompareOut), _vp]),

@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CSrcBatch,
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CSrcBatch,
                   CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -486,6 +486,58 @@ class CompareBuffers:
             return flags, summary, None
         nw = int(_np(self.n_work, U32)[0])
         return flags, summary, _np(self.worklist, U32)[:nw]
+
+
+class DiffBuffers:
+    """Outputs of a merge diff (crdt_diff_out): flags (u8 per doc, OR of CRDT_DIFF_*),
+    summary (5 counts), and the two packed lists with their [n_docs + 1] exclusive
+    offsets: removed (rem_off, rem_keys, rem_actors, rem_counters; rem_slots entries of
+    room) and upserted (ups_off, ups_keys, ups_actors, ups_counters, ups_kind; ups_slots).
+    dots / kind False: those columns are not asked for.  numpy, or torch on `device`."""
+
+    def __init__(self, n_docs, rem_slots, ups_slots, device=None, dots=True, kind=True, summary=True):
+        self.n_docs = n = int(n_docs)
+        self.rem_slots, self.ups_slots = nr, nu = int(rem_slots), int(ups_slots)
+        if device is None:
+            z = lambda k, dt: np.zeros(max(k, 1), dt)  # noqa: E731
+            u8, u32, u64 = np.uint8, U32, U64
+        else:
+            import torch
+
+            z = lambda k, dt: torch.empty(max(k, 1), dtype=dt, device=device)  # noqa: E731
+            u8, u32, u64 = torch.uint8, torch.int32, torch.int64
+        self.flags = z(n, u8)
+        self.summary = z(5, u32) if summary else None
+        self.rem_off, self.ups_off = z(n + 1, u32), z(n + 1, u32)
+        self.rem_keys, self.ups_keys = z(nr, u64), z(nu, u64)
+        self.rem_actors = z(nr, u32) if dots else None
+        self.rem_counters = z(nr, u64) if dots else None
+        self.ups_actors = z(nu, u32) if dots else None
+        self.ups_counters = z(nu, u64) if dots else None
+        self.ups_kind = z(nu, u8) if kind else None
+
+    FIELDS = ("flags", "summary", "rem_off", "rem_keys", "rem_actors", "rem_counters", "ups_off", "ups_keys",
+              "ups_actors", "ups_counters", "ups_kind")
+
+    def c(self) -> CDiffOut:
+        return CDiffOut(*(ptr(getattr(self, f)) for f in self.FIELDS))
+
+    def numpy(self):
+        """A dict of numpy arrays: flags [n_docs], summary [5] or None, the offsets
+        [n_docs + 1], and each list's columns trimmed to min(total, slots) (absent: None)."""
+        n = self.n_docs
+        out = {"flags": _np(self.flags, np.uint8)[:n],
+               "summary": None if self.summary is None else _np(self.summary, U32)[:5]}
+        for side, slots in (("rem", self.rem_slots), ("ups", self.ups_slots)):
+            off = _np(getattr(self, side + "_off"), U32)[: n + 1]
+            m = min(int(off[n]), slots)
+            out[side + "_off"] = off
+            for col, dt in (("keys", U64), ("actors", U32), ("counters", U64)):
+                a = getattr(self, "%s_%s" % (side, col))
+                out["%s_%s" % (side, col)] = None if a is None else _np(a, dt)[:m]
+            if side == "ups":
+                out["ups_kind"] = None if self.ups_kind is None else _np(self.ups_kind, np.uint8)[:m]
+        return out
 
 
 def c_ref(x):

@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -158,6 +158,20 @@ class Engine:
         ca, cb, co = _c(a), _c(b), _c(out)
         check(self._lib.crdt_awset_compare_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb), int(mask),
                                                  ctypes.byref(co), _stream(stream)), "crdt_awset_compare_async")
+
+    def diff_async(self, before: AWSetBatch, after: AWSetBatch, out: DiffBuffers, rem_slots=None, ups_slots=None,
+                   stream=None):
+        """Per doc, what turns before[d] into after[d]: the removed entries and the upserted
+        ones (ADDED / UPDATED), each list packed in key order behind exclusive offsets, and
+        CRDT_DIFF_* flags (crdt_awset_diff_async).  A total above out's rem_slots / ups_slots:
+        CRDT_E_CAPACITY at sync, offsets and totals exact, nothing written past the slots.
+        The slot limits default to the sizes out was made with."""
+        cb, ca, co = _c(before), _c(after), _c(out)
+        rem_slots = out.rem_slots if rem_slots is None else rem_slots
+        ups_slots = out.ups_slots if ups_slots is None else ups_slots
+        check(self._lib.crdt_awset_diff_async(self._ctx, ctypes.byref(cb), ctypes.byref(ca), int(rem_slots),
+                                              int(ups_slots), ctypes.byref(co), _stream(stream)),
+              "crdt_awset_diff_async")
 
     def digest_async(self, state: AWSetBatch, out, tombs: TombBatch = None, stream=None):
         """Per doc, the 16-byte digest of its live state into `out` (device u64 [2 * n_docs]):
@@ -362,6 +376,19 @@ class Engine:
         ca, cb, co = a.c(), b.c(), out.c()
         check(self._lib.crdt_awset_compare_batch(self._ctx, ctypes.byref(ca), ctypes.byref(cb), int(mask),
                                                  ctypes.byref(co)), "crdt_awset_compare_batch")
+        return out.numpy()
+
+    def diff(self, before: AWSetBatch, after: AWSetBatch):
+        """Host buffers: DiffBuffers.numpy() of the diff, its lists sized from the totals
+        (crdt_awset_diff_batch; for tests and small callers).  One call with a worst-case
+        allocation, not a sizing call and an emitting call: a removed record is a live entry
+        of `before` and an upsert a live entry of `after`, so the live counts bound the
+        totals, and only the first `total` words of each list are downloaded."""
+        before, after = before.numpy(), after.numpy()
+        out = DiffBuffers(before.n_docs, before.live_slots(), after.live_slots())
+        cb, ca, co = before.c(), after.c(), out.c()
+        check(self._lib.crdt_awset_diff_batch(self._ctx, ctypes.byref(cb), ctypes.byref(ca), out.rem_slots,
+                                              out.ups_slots, ctypes.byref(co)), "crdt_awset_diff_batch")
         return out.numpy()
 
     def fold(self, mode: int, dst: AWSetBatch, srcs: SrcBatch, pinned: bool = False) -> OutBuffers:

@@ -52,6 +52,10 @@ hipError_t launch_select(const BatchView& st, const uint32_t* idx, const uint32_
 hipError_t launch_scatter(const BatchView& st, const BatchView& sub, const uint32_t* idx, const uint32_t* n_idx,
                           uint32_t out_slots, const OutView& out, uint32_t* inv, uint32_t* parts, uint32_t* status,
                           uint32_t n_cu, hipStream_t stream);
+size_t diff_parts_bytes();
+hipError_t launch_diff(const BatchView& before, const BatchView& after, uint32_t rem_slots, uint32_t ups_slots,
+                       const DiffOutView& out, uint32_t* fw, uint32_t* parts, uint32_t* status, const uint32_t* gate,
+                       uint32_t n_cu, hipStream_t stream);
 hipError_t launch_sources(const SourcesArgs& s, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status, uint32_t n_cu,
                           hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
@@ -331,6 +335,32 @@ bool batch_ptrs_ok(const crdt_awset_batch* b) {
 
 bool out_ptrs_ok(const crdt_awset_out* o) {
     return o && o->offsets && o->counts && o->keys && o->actors && o->counters && o->vv;
+}
+
+// crdt_diff_out against the two inputs (include/crdtgpu.h): required pointers,
+// the dots of a list both or neither, and no out array starting where an input
+// array of the same kind (or the other list's column) starts.
+bool diff_out_ok(const crdt_diff_out* o, const crdt_awset_batch* before, const crdt_awset_batch* after,
+                 uint32_t rem_slots, uint32_t ups_slots) {
+    if (!o || !o->flags || !o->rem_off || !o->ups_off) return false;
+    if ((rem_slots && !o->rem_keys) || (ups_slots && !o->ups_keys)) return false;
+    if ((o->rem_actors == nullptr) != (o->rem_counters == nullptr)) return false;
+    if ((o->ups_actors == nullptr) != (o->ups_counters == nullptr)) return false;
+    if (o->rem_off == o->ups_off) return false;
+    if (o->rem_keys && (o->rem_keys == o->ups_keys || o->rem_keys == o->rem_counters || o->rem_keys == o->ups_counters))
+        return false;
+    if (o->ups_keys && (o->ups_keys == o->rem_counters || o->ups_keys == o->ups_counters)) return false;
+    if (o->rem_actors && o->rem_actors == o->ups_actors) return false;
+    if (o->rem_counters && o->rem_counters == o->ups_counters) return false;
+    for (const crdt_awset_batch* b : {before, after}) {
+        for (const uint32_t* w : {(const uint32_t*)o->rem_off, (const uint32_t*)o->ups_off, (const uint32_t*)o->summary,
+                                  (const uint32_t*)o->rem_actors, (const uint32_t*)o->ups_actors})
+            if (w && (w == b->offsets || w == b->counts || w == b->actors)) return false;
+        for (const uint64_t* w : {(const uint64_t*)o->rem_keys, (const uint64_t*)o->ups_keys,
+                                  (const uint64_t*)o->rem_counters, (const uint64_t*)o->ups_counters})
+            if (w && (w == b->keys || w == b->counters || w == b->vv)) return false;
+    }
+    return true;
 }
 
 bool src_ptrs_ok(const crdt_src_batch* s) {
@@ -822,6 +852,32 @@ int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const
     if (rc != CRDT_OK) return rc;
     rc = hip_err(launch_scatter(view(state), view(sub), idx, n_idx, out_slots, view(out), ctx->worklist.as<uint32_t>(),
                                 ctx->defer.as<uint32_t>(), make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Merge diff (diff.hip): the per-document flag words the count pass ORs into live
+// in the defer buffer, one word per document, which is what
+// crdt_ctx_reserve(max_docs, ..) sizes it for; the partial sums of the two lists
+// (a fixed 3 x 2,048 words, whatever the batches hold) in the context-partials
+// buffer, allocated once at crdt_ctx_create.
+int crdt_awset_diff_async(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
+                          uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out, void* stream) {
+    if (!ctx || !batch_ptrs_ok(before) || !batch_ptrs_ok(after)) return CRDT_E_INVALID;
+    if (before->n_docs != after->n_docs || before->R != after->R) return CRDT_E_INVALID;
+    if (!diff_out_ok(out, before, after, rem_slots, ups_slots)) return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(before->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK && ctx->parts.bytes < diff_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (rc != CRDT_OK) return rc;
+    const Work wk = make_work(ctx);
+    const DiffOutView ov{out->flags,      out->summary,  out->rem_off,    out->rem_keys,     out->rem_actors, out->rem_counters,
+                         out->ups_off,    out->ups_keys, out->ups_actors, out->ups_counters, out->ups_kind};
+    rc = hip_err(launch_diff(view(before), view(after), rem_slots, ups_slots, ov, ctx->defer.as<uint32_t>(),
+                             ctx->parts.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 
@@ -1827,6 +1883,70 @@ int crdt_awset_compare_batch(crdt_ctx* ctx, const crdt_awset_batch* a, const crd
     if (rc == CRDT_OK && out->worklist) *out->n_work = nw;
     sync = crdt_ctx_sync(ctx, ctx->stream);
     return rc != CRDT_OK ? rc : sync;
+}
+
+// For tests and small callers (include/crdtgpu.h): the slot layouts are checked
+// here, the key order on the device; batches out of order reach no diff
+// (Work::gate).  Only flags, summary, the offsets and the live part of each list
+// come back: never a state.
+int crdt_awset_diff_batch(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
+                          uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out) {
+    if (!ctx || !out) return CRDT_E_INVALID;
+    int rc = validate_batch(before, false);
+    if (rc == CRDT_OK) rc = validate_batch(after, false);
+    if (rc != CRDT_OK) return rc;
+    if (before->n_docs != after->n_docs || before->R != after->R) return CRDT_E_INVALID;
+    if (!diff_out_ok(out, before, after, rem_slots, ups_slots)) return CRDT_E_INVALID;
+    const uint32_t n = before->n_docs;
+    if ((rc = set_device(ctx)) != CRDT_OK) return rc;
+    Stager st{ctx};
+    crdt_awset_batch db = *before, da = *after;
+    st.plan([&] {
+        db = stage_batch(st, before);
+        da = stage_batch(st, after);
+    });
+    crdt_diff_out dout{};
+    dout.flags = st.room<uint8_t>(n);
+    dout.summary = out->summary ? st.room<uint32_t>(5) : nullptr;
+    dout.rem_off = st.room<uint32_t>((size_t)n + 1);
+    dout.ups_off = st.room<uint32_t>((size_t)n + 1);
+    dout.rem_keys = st.room<uint64_t>(rem_slots);
+    dout.ups_keys = st.room<uint64_t>(ups_slots);
+    if (out->rem_actors) {
+        dout.rem_actors = st.room<uint32_t>(rem_slots);
+        dout.rem_counters = st.room<uint64_t>(rem_slots);
+    }
+    if (out->ups_actors) {
+        dout.ups_actors = st.room<uint32_t>(ups_slots);
+        dout.ups_counters = st.room<uint64_t>(ups_slots);
+    }
+    dout.ups_kind = out->ups_kind ? st.room<uint8_t>(ups_slots) : nullptr;
+    st.flush();  // the inputs' span, if they lie in one crdt_host_alloc block
+    if (st.rc != CRDT_OK) return st.rc;
+    rc = check_order(ctx, {{db.offsets, db.counts, n, db.keys}, {da.offsets, da.counts, n, da.keys}});
+    if (rc == CRDT_OK)
+        rc = gated(ctx, [&] { return crdt_awset_diff_async(ctx, &db, &da, rem_slots, ups_slots, &dout, ctx->stream); });
+    uint32_t tot[2] = {0, 0};
+    if (rc == CRDT_OK) rc = get(&tot[0], dout.rem_off + n, 1, ctx->stream);
+    if (rc == CRDT_OK) rc = get(&tot[1], dout.ups_off + n, 1, ctx->stream);
+    int sync = crdt_ctx_sync(ctx, ctx->stream);  // (an order violation ends the call here)
+    if (rc != CRDT_OK) return rc;
+    if (sync != CRDT_OK && sync != CRDT_E_CAPACITY) return sync;
+    const int verdict = sync;  // CRDT_E_CAPACITY: a list did not fit; the offsets and totals still come back
+    const size_t nr = std::min(tot[0], rem_slots), nu = std::min(tot[1], ups_slots);
+    rc = get(out->flags, dout.flags, n, ctx->stream);
+    if (rc == CRDT_OK && out->summary) rc = get(out->summary, dout.summary, 5, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->rem_off, dout.rem_off, (size_t)n + 1, ctx->stream);
+    if (rc == CRDT_OK) rc = get(out->ups_off, dout.ups_off, (size_t)n + 1, ctx->stream);
+    if (rc == CRDT_OK && out->rem_keys) rc = get(out->rem_keys, dout.rem_keys, nr, ctx->stream);
+    if (rc == CRDT_OK && out->rem_actors) rc = get(out->rem_actors, dout.rem_actors, nr, ctx->stream);
+    if (rc == CRDT_OK && out->rem_counters) rc = get(out->rem_counters, dout.rem_counters, nr, ctx->stream);
+    if (rc == CRDT_OK && out->ups_keys) rc = get(out->ups_keys, dout.ups_keys, nu, ctx->stream);
+    if (rc == CRDT_OK && out->ups_actors) rc = get(out->ups_actors, dout.ups_actors, nu, ctx->stream);
+    if (rc == CRDT_OK && out->ups_counters) rc = get(out->ups_counters, dout.ups_counters, nu, ctx->stream);
+    if (rc == CRDT_OK && out->ups_kind) rc = get(out->ups_kind, dout.ups_kind, nu, ctx->stream);
+    sync = crdt_ctx_sync(ctx, ctx->stream);
+    return rc != CRDT_OK ? rc : (sync != CRDT_OK ? sync : verdict);
 }
 
 }  // extern "C"

@@ -190,6 +190,22 @@ struct CompareOutView {
     uint32_t* n_work;
 };
 
+// Merge diff (diff.hip): what crdt_awset_diff_async writes (same fields as
+// crdt_diff_out).
+struct DiffOutView {
+    uint8_t* flags;
+    uint32_t* summary;  // NULL: none
+    uint32_t* rem_off;
+    uint64_t* rem_keys;
+    uint32_t* rem_actors;  // NULL: no dots (then rem_counters too)
+    uint64_t* rem_counters;
+    uint32_t* ups_off;
+    uint64_t* ups_keys;
+    uint32_t* ups_actors;  // NULL: no dots (then ups_counters too)
+    uint64_t* ups_counters;
+    uint8_t* ups_kind;  // NULL: none
+};
+
 // Workspace of the large-document tile path (tile.hip).  A call's tiles are
 // numbered 0 .. total-1 over all its documents and run in passes of at most
 // `cap` tiles (pass p: tiles [p*cap, p*cap + cap)); the per-tile arrays hold

@@ -701,6 +701,81 @@ func (b *HostBatch) Digest() ([][2]uint64, error) {
 	return out, nil
 }
 
+// ---------------------------------------------------------------- merge diff
+
+// DocDiff is what turns one document's `before` into its `after`: merge's
+// decision log (awset.go:109-158) in structured form. Removed holds the entries
+// of before whose key after no longer has, with the dot they had; Added the
+// entries of after under a key before did not have; Updated the entries of after
+// whose key before had under another dot. Deleting Removed from before and then
+// assigning Added and Updated gives after. Clock: the version vectors differ.
+type DocDiff struct {
+	Removed map[string]crdt.Dot
+	Added   map[string]crdt.Dot
+	Updated map[string]crdt.Dot
+	Clock   bool
+}
+
+// DiffBatch computes DocDiff of (before[i], after[i]) for every i in one call
+// (crdt_awset_diff_batch): both batches go up, only the two lists, their offsets
+// and a flag byte per document come back. The lists are sized for the worst case
+// (every entry of before removed, every entry of after upserted), so one call
+// suffices. It reads the states and changes neither.
+func (e *Engine) DiffBatch(before, after []*crdt.AWSet) ([]DocDiff, error) {
+	if len(before) != len(after) {
+		return nil, fmt.Errorf("DiffBatch: %d and %d states", len(before), len(after))
+	}
+	n := len(before)
+	if n == 0 {
+		return nil, nil
+	}
+	keys := make([]docKeys, n)
+	R := 1
+	for i := range before {
+		keys[i] = internDoc(before[i].Entries, after[i].Entries)
+		R = max(R, len(before[i].VersionVector), len(after[i].VersionVector))
+	}
+	var a arena
+	defer a.free()
+	cb, boff := a.batch(before, keys, R)
+	ca, aoff := a.batch(after, keys, R)
+	nr, nu := int(boff[n]), int(aoff[n])
+	flags := a.u32((n + 3) / 4) // one byte per document
+	remOff, upsOff := a.u32(n+1), a.u32(n+1)
+	rem, ups := a.entries(nr+1), a.entries(nu+1)
+	kind := a.u32((nu + 3) / 4) // one byte per upsert
+	if a.err != nil {
+		return nil, a.err
+	}
+	cdiff := C.crdt_diff_out{flags: (*C.uint8_t)(unsafe.Pointer(p32(flags))),
+		rem_off: p32(remOff), rem_keys: p64(rem.keys), rem_actors: p32(rem.actors), rem_counters: p64(rem.counters),
+		ups_off: p32(upsOff), ups_keys: p64(ups.keys), ups_actors: p32(ups.actors), ups_counters: p64(ups.counters),
+		ups_kind: (*C.uint8_t)(unsafe.Pointer(p32(kind)))}
+	if rc := C.crdt_awset_diff_batch(e.ctx, &cb, &ca, C.uint32_t(nr), C.uint32_t(nu), &cdiff); rc != 0 {
+		return nil, errOf("crdt_awset_diff_batch", rc)
+	}
+	flagOf := unsafe.Slice((*uint8)(unsafe.Pointer(unsafe.SliceData(flags))), n)
+	kindOf := unsafe.Slice((*uint8)(unsafe.Pointer(unsafe.SliceData(kind))), nu+1)
+	res := make([]DocDiff, n)
+	for d := range res {
+		r := DocDiff{Removed: map[string]crdt.Dot{}, Added: map[string]crdt.Dot{}, Updated: map[string]crdt.Dot{},
+			Clock: flagOf[d]&uint8(C.CRDT_DIFF_CLOCK) != 0}
+		for j := remOff[d]; j < remOff[d+1]; j++ {
+			r.Removed[keys[d][rem.keys[j]]] = crdt.Dot{Actor: crdt.Actor(rem.actors[j]), Counter: uint(rem.counters[j])}
+		}
+		for j := upsOff[d]; j < upsOff[d+1]; j++ {
+			dot := crdt.Dot{Actor: crdt.Actor(ups.actors[j]), Counter: uint(ups.counters[j])}
+			if kindOf[j] == uint8(C.CRDT_DIFF_UPDATED) {
+				r.Updated[keys[d][ups.keys[j]]] = dot
+			} else {
+				r.Added[keys[d][ups.keys[j]]] = dot
+			}
+		}
+		res[d] = r
+	}
+	return res, nil
+}
+
 // foldWidth is len(dst.VersionVector) after the fold, replayed on the clocks
 // alone: every AWSet step merges the clock; a delta step merges it unless it
 // is the no-op (awset-delta_test.go:60): Counter(src.Actor) != 0 (:53) and

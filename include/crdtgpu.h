@@ -44,6 +44,10 @@
  *   crdt_awset_scatter_async
  *       the merged sub-batch written back into the batch it was selected
  *       from: select's inverse (no reference counterpart)
+ *   crdt_awset_diff_async / crdt_awset_diff_batch
+ *       replace merge's decision log (update / add / remove per key,
+ *       awset.go:109-158) in structured form: per document, the entries a
+ *       merge removed and the entries it added or moved to another dot
  *   crdt_awset_sources_async
  *       P resident replicas of every document gathered into the packed source
  *       batch the folds and the delta extraction read (no reference
@@ -635,6 +639,87 @@ int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const 
 int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_awset_batch* sub,
                              const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */,
                              uint32_t out_slots, const crdt_awset_out* out, void* stream);
+
+/* ---- merge diff: what a merge changed, per document -------------------------
+ * Every merge call answers "what is the merged state"; this one answers "what
+ * did the merge change".  The reference prints it per key as merge's decision
+ * log -- update, add, skip, remove, keep (awset.go:109-158); this is its
+ * structured form, for whoever keeps something beside the set (an index, a view,
+ * a subscriber list) and for a host boundary that applies a merge output to Go
+ * maps: only the lists need to cross PCIe, not the merged state.
+ * before and after are two batches with the same n_docs and R.  Their slot
+ * layouts are independent; either may have counts, slack, or documents at
+ * capacity offsets: a join, exchange, fold, apply, select or scatter output is
+ * valid as it stands.  Only live prefixes are read (the first counts[d] slots of
+ * a document, all slots when counts == NULL); slack is never read, whatever it
+ * holds.  The entries need no clock: only the CLOCK flag reads the vv.
+ * Per document d:
+ *   - removed: the live entries of before[d] whose key is not a live key of
+ *     after[d], in key order, with the dot they had in before (the log's
+ *     phase-2 `remove`, awset.go:145-158).
+ *   - upserted: the live entries of after[d] whose key is not live in before[d]
+ *     (kind CRDT_DIFF_ADDED: the log's `add`) or is live there under a different
+ *     (actor, counter) (kind CRDT_DIFF_UPDATED: the log's `update`), in key
+ *     order, with the dot they have in after.
+ *     Deleting `removed` from before[d] and then assigning `upserted` gives
+ *     exactly after[d]'s live entries.
+ *   - flags[d] is the OR of CRDT_DIFF_REMOVED | CRDT_DIFF_ADDED |
+ *     CRDT_DIFF_UPDATED for the kinds present, plus CRDT_DIFF_CLOCK when any of
+ *     the R clock words differs.  flags[d] == 0 iff live state and VV are
+ *     bit-identical: the same statement as crdt_awset_compare_*'s flags[d] == 0.
+ *   - Both lists are packed with no slack: rem_off / ups_off are [n_docs + 1]
+ *     exclusive prefixes and the last word is the total.  The offsets and the
+ *     totals are exact even when a total exceeds the caller's rem_slots /
+ *     ups_slots: crdt_ctx_sync then returns CRDT_E_CAPACITY, nothing is written
+ *     at or past the slots given (the other list is complete), and the caller
+ *     can read the totals, resize and call again.  rem_slots == 0 and ups_slots
+ *     == 0 with NULL lists is the sizing call.
+ *   - summary (optional): [0] removed records, [1] upsert records, [2] upsert
+ *     records that are UPDATED, [3] documents with an entry change, [4]
+ *     documents with flags != 0.
+ *   - The output is the same bits on every run: no atomic decides a position.
+ *   - A live count above a document's slots is clamped to them and crdt_ctx_sync
+ *     returns CRDT_E_CAPACITY, as in crdt_awset_compare_async.
+ * Returned by the call (CRDT_E_INVALID): before, after or out NULL; flags,
+ * rem_off or ups_off NULL; rem_keys NULL with rem_slots > 0, ups_keys NULL with
+ * ups_slots > 0; exactly one of a list's actors / counters NULL; an n_docs or R
+ * mismatch, R out of range; an out array starting where an input array of the
+ * same kind starts (offsets and counts against rem_off / ups_off; keys, actors,
+ * counters against the lists' columns), or the two lists sharing a column.
+ * n_docs == 0: rem_off[0], ups_off[0] and summary are written (zeros) and
+ * nothing else; nothing that reads documents is launched.
+ * Callers compose, this call does not: there is no idx argument.  To diff only
+ * the documents a compare or digest worklist names, crdt_awset_select_async both
+ * sides with that worklist first and diff the two selections.
+ * _async: no host sync, kernel nodes only, capturable; ordered after the
+ * context's previous call like every entry point.  Workspace: one flag word per
+ * document, in the buffer crdt_ctx_reserve(max_docs, ..) sizes (no allocation
+ * on a reserved context, CRDT_E_WORKSPACE when it would have to grow during a
+ * graph capture), and a fixed 24 KB of partial sums the context owns from its
+ * creation.
+ * _batch (host arrays; for tests and small callers): checks the slot layouts
+ * and counts on the host (CRDT_E_INVALID / CRDT_E_CAPACITY), the key order on the
+ * device after the upload (CRDT_E_UNSORTED: no diff runs, out untouched), and
+ * downloads only flags, summary, the offsets and the first min(total, slots)
+ * words of each list, never a state.  A total above its slots returns
+ * CRDT_E_CAPACITY after that download, so the totals can be read. */
+#define CRDT_DIFF_REMOVED 1u /* a live key of before[d] is not live in after[d]       */
+#define CRDT_DIFF_ADDED   2u /* a live key of after[d] is not live in before[d]       */
+#define CRDT_DIFF_UPDATED 4u /* a key live in both, under different (actor, counter)  */
+#define CRDT_DIFF_CLOCK   8u /* before.vv[r] != after.vv[r] for some r < R            */
+typedef struct {            /* written */
+    uint8_t*  flags;        /* [n_docs] OR of CRDT_DIFF_* for doc d */
+    uint32_t* summary;      /* [5], may be NULL */
+    uint32_t* rem_off;      /* [n_docs+1] */
+    uint64_t* rem_keys;  uint32_t* rem_actors;  uint64_t* rem_counters;   /* dots: both or neither NULL */
+    uint32_t* ups_off;      /* [n_docs+1] */
+    uint64_t* ups_keys;  uint32_t* ups_actors;  uint64_t* ups_counters;
+    uint8_t*  ups_kind;     /* [ups total] CRDT_DIFF_ADDED | CRDT_DIFF_UPDATED, may be NULL */
+} crdt_diff_out;
+int crdt_awset_diff_async(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
+                          uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out, void* stream);
+int crdt_awset_diff_batch(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
+                          uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out);
 
 /* ---- sources: resident replicas assembled into a fold / extraction input ----
  * Replicas live on the device as state batches (crdt_awset_batch, plus
