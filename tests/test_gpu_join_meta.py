@@ -118,13 +118,11 @@ def test_join_and_exchange_partial_waves(k_eng, torch, n, slack):
         eng.set_max_doc_entries()
 
 
-def test_large_documents_at_wave_lane_edges(k_eng, torch):
-    """Documents above 64 entries at lane 0 of a wave, at lane cnt - 1 of a full
-    and of a partly filled wave, and the last document, with the promise of
-    small documents unset: each reaches the worklist of the tile path once and
-    comes out equal to the oracle, join and exchange."""
-    eng, K = k_eng
-    n = 127
+@functools.lru_cache(maxsize=None)
+def lane_edge_case(K, n=127):
+    """n pairs with documents above 64 entries at lane 0 of a wave, at lane
+    cnt - 1 of a full and of a partly filled wave of K documents, and the last
+    document; with the oracle's join in both directions."""
     per = WAVES * K
     last_block = (n - 1) // per * per
     last_wave = last_block + min(WAVES, n - last_block) - 1  # first document of the last wave that has any
@@ -139,6 +137,16 @@ def test_large_documents_at_wave_lane_edges(k_eng, torch):
     rc1, ab = oracle.join(a, b)
     rc2, ba = oracle.join(b, a)
     assert rc1 == 0 and rc2 == 0
+    return a, b, ab, ba
+
+
+def test_large_documents_at_wave_lane_edges(k_eng, torch):
+    """Documents above 64 entries at the lane edges of lane_edge_case, with the
+    promise of small documents unset: each reaches the worklist of the tile path
+    once and comes out equal to the oracle, join and exchange."""
+    eng, K = k_eng
+    a, b, ab, ba = lane_edge_case(K)
+    n = a.n_docs
     dev = torch.device("cuda:0")
     da, db = a.to(dev), b.to(dev)
     slots = int(a.offsets[-1]) + int(b.offsets[-1])

@@ -46,7 +46,7 @@ def eng(torch):
 
 # every tile shape (threads x positions; look-back per tile or deferred by one)
 # must give the same bits
-SHAPES = [9, 0, 1, 2, 3, 4, 5, 6, 7, 8]
+SHAPES = [9, 0, 1, 2, 3, 4, 5, 6, 7, 8, 10]
 
 
 @pytest.fixture(params=SHAPES, ids=lambda s: "shape%d" % s)
@@ -179,10 +179,13 @@ def test_tile_one_document_of_a_million(shaped):
     check_join_and_exchange(shaped, a, b, R)
 
 
-def host_tiles(a, b, tile=TILE // 2):
-    """Tiles a join of host batches a <- b has (tile.hip: ceil((nd + ns) / T) per
-    document with more than 64 live entries on a side; T = 1024 for the default
-    shape)."""
+def host_tiles(a, b, shape=DEFAULT_SHAPE):
+    """Tiles a join of host batches a <- b has at a tile shape (api.cpp, host_tiles:
+    ceil((nd + ns) / T) per document with more than 64 live entries on a side, T
+    the shape's merged positions per tile)."""
+    from join_option_cases import T_OF_SHAPE  # (that module takes its generators from this one)
+
+    tile = T_OF_SHAPE[shape]
     nd = np.array([a.live(d) for d in range(a.n_docs)], dtype=np.int64)
     ns = np.array([b.live(d) for d in range(b.n_docs)], dtype=np.int64)
     big = (nd > 64) | (ns > 64)
