@@ -212,6 +212,9 @@ def signatures():
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_sources_async": (ctypes.c_int, [_vp, P(CReplica), _u32, _u32, _u32, P(CDeltaOut), _vp]),
+        "crdt_awset_delta_join_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CReplica), P(CAWSetOut), _vp, _vp]),
+        "crdt_awset_delta_exchange_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), P(CAWSetOut), P(CAWSetOut),
+                                                           _vp, _vp, _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

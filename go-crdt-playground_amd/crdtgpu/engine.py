@@ -263,6 +263,47 @@ class Engine:
         return SrcBatch(R, h.doc_srcs, h.src_actor, h.vv[: n * P * R], h.entry_off, h.keys[:te], h.actors[:te],
                         h.counters[:te], h.tomb_off, h.tkeys[:tt], h.tactors[:tt], h.tcounters[:tt])
 
+    def delta_join_async(self, dst: AWSetBatch, src, out: OutBuffers, kind=None, stream=None):
+        """out[d] = dst[d] <- src[d] by (*AWSetDelta).Merge, src a resident Replica as it
+        stands (crdt_awset_delta_join_async); kind: device u8 per doc, CRDT_DELTA_*, or None."""
+        d, s, o = _c(dst), _c(src), _c(out)
+        check(self._lib.crdt_awset_delta_join_async(self._ctx, ctypes.byref(d), ctypes.byref(s), ctypes.byref(o),
+                                                    ptr(kind), _stream(stream)), "crdt_awset_delta_join_async")
+
+    def delta_exchange_async(self, a, b, out_ab: OutBuffers, out_ba: OutBuffers, kind_ab=None, kind_ba=None,
+                             stream=None):
+        """Both AWSetDelta merges of a resident Replica pair from one read of both:
+        out_ab = a <- b and out_ba = b <- a, in the join's layout
+        (crdt_awset_delta_exchange_async); kind_ab / kind_ba: device u8 per doc, or None."""
+        ca, cb, o1, o2 = _c(a), _c(b), _c(out_ab), _c(out_ba)
+        check(self._lib.crdt_awset_delta_exchange_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb),
+                                                        ctypes.byref(o1), ctypes.byref(o2), ptr(kind_ab),
+                                                        ptr(kind_ba), _stream(stream)),
+              "crdt_awset_delta_exchange_async")
+
+    def delta_exchange(self, a, b):
+        """Host replicas uploaded, exchanged on the device and downloaded: (out_ab, out_ba,
+        kind_ab, kind_ba), the outputs as host OutBuffers and the kinds as numpy uint8 arrays
+        (for tests and small callers: a caller who holds host data builds a source batch and folds)."""
+        import numpy as np
+        import torch
+
+        a, b = a.numpy(), b.numpy()
+        n, R = a.n_docs, a.state.R
+        slots = int(a.state.offsets[-1]) + int(b.state.offsets[-1])
+        dev = torch.device("cuda", self.device)
+        outs = [OutBuffers(n, R, slots, device=dev) for _ in range(2)]
+        kinds = [torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.delta_exchange_async(a.to(dev), b.to(dev), outs[0], outs[1], kinds[0], kinds[1])
+        self.sync()
+        host = []
+        for o in outs:
+            h = OutBuffers(n, R, slots)
+            h.offsets, h.counts, h.vv = _np(o.offsets, np.uint32), _np(o.counts, np.uint32), _np(o.vv, np.uint64)
+            h.keys, h.actors, h.counters = _np(o.keys, np.uint64), _np(o.actors, np.uint32), _np(o.counters, np.uint64)
+            host.append(h)
+        return host[0], host[1], _np(kinds[0], np.uint8)[:n], _np(kinds[1], np.uint8)[:n]
+
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),
               "crdt_vv_min_async")

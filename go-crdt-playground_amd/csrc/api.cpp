@@ -58,6 +58,9 @@ hipError_t launch_diff(const BatchView& before, const BatchView& after, uint32_t
                        uint32_t n_cu, hipStream_t stream);
 hipError_t launch_sources(const SourcesArgs& s, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status, uint32_t n_cu,
                           hipStream_t stream);
+hipError_t launch_delta_pair(const PairSide& A, const PairSide& B, const OutView& out_ab, const OutView* out_ba,
+                             uint8_t* kind_ab, uint8_t* kind_ba, const Work& wk, uint32_t block_grid,
+                             hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
                          uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
@@ -934,6 +937,101 @@ int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n
     rc = hip_err(launch_sources(a, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(), make_work(ctx).status,
                                 (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
+}
+
+// Delta merge of a resident pair (delta_pair.hip).  Workspace: the join's
+// worklist, one word per document, which crdt_ctx_reserve(max_docs, ..) sizes.
+// a_tombs / a_doc_actor / a_actor: replica a beyond its state (the exchange);
+// out_ba == NULL: the join, which reads none of them.
+static int delta_pair_common(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_tomb_batch* a_tombs,
+                             const uint32_t* a_doc_actor, uint32_t a_actor, const crdt_replica* b,
+                             const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
+                             uint8_t* kind_ba, void* stream) {
+    if (!ctx || !batch_ptrs_ok(a) || !b || !batch_ptrs_ok(b->state) || !out_ptrs_ok(out_ab) ||
+        (out_ba && !out_ptrs_ok(out_ba)))
+        return CRDT_E_INVALID;
+    const crdt_awset_batch* bs = b->state;
+    if (a->n_docs != bs->n_docs || a->R != bs->R) return CRDT_E_INVALID;
+    if ((a_tombs && !a_tombs->offsets) || (b->tombs && !b->tombs->offsets)) return CRDT_E_INVALID;
+    // No two output arrays start at one address (the two directions keep different
+    // keys: there is no shared key column), the per-document arrays, whose sizes
+    // the host knows, do not overlap at all, and no output array starts where an
+    // input array of the same kind starts.
+    const size_t n = a->n_docs, R = a->R;
+    struct Range {
+        uintptr_t p;
+        size_t bytes;  // 0: size unknown here (entry arrays)
+    };
+    Range r[12];
+    int nr = 0;
+    for (const crdt_awset_out* o : {out_ab, out_ba}) {
+        if (!o) continue;
+        r[nr++] = {(uintptr_t)o->offsets, (n + 1) * 4};
+        r[nr++] = {(uintptr_t)o->counts, n * 4};
+        r[nr++] = {(uintptr_t)o->vv, n * R * 8};
+        r[nr++] = {(uintptr_t)o->keys, 0};
+        r[nr++] = {(uintptr_t)o->actors, 0};
+        r[nr++] = {(uintptr_t)o->counters, 0};
+    }
+    for (int i = 0; i < nr; ++i)
+        for (int j = i + 1; j < nr; ++j) {
+            if (r[i].p == r[j].p) return CRDT_E_INVALID;
+            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
+                return CRDT_E_INVALID;
+        }
+    if (kind_ab && kind_ab == kind_ba) return CRDT_E_INVALID;
+    const crdt_tomb_batch* tb[2] = {a_tombs, b->tombs};
+    const crdt_awset_batch* st[2] = {a, bs};
+    const uint32_t* da[2] = {a_doc_actor, b->doc_actor};
+    for (const crdt_awset_out* o : {out_ab, out_ba}) {
+        if (!o) continue;
+        for (int p = 0; p < 2; ++p) {
+            for (const uint32_t* w : {(const uint32_t*)o->offsets, (const uint32_t*)o->counts, (const uint32_t*)o->actors}) {
+                if (w == st[p]->offsets || w == st[p]->counts || w == st[p]->actors || w == da[p]) return CRDT_E_INVALID;
+                if (tb[p] && (w == tb[p]->offsets || w == tb[p]->counts || w == tb[p]->actors)) return CRDT_E_INVALID;
+            }
+            for (const uint64_t* w : {(const uint64_t*)o->keys, (const uint64_t*)o->counters, (const uint64_t*)o->vv}) {
+                if (w == st[p]->keys || w == st[p]->counters || w == st[p]->vv) return CRDT_E_INVALID;
+                if (tb[p] && (w == tb[p]->keys || w == tb[p]->counters)) return CRDT_E_INVALID;
+            }
+        }
+    }
+    if (a->n_docs == 0) return CRDT_OK;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    if (launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
+    auto side = [](const crdt_awset_batch* st_, const crdt_tomb_batch* t, const uint32_t* doc_actor, uint32_t actor) {
+        PairSide ps{};
+        ps.st = view(st_);
+        if (t) ps.tb = TombView{t->offsets, t->counts, t->keys, t->actors, t->counters};
+        ps.doc_actor = doc_actor;
+        ps.actor = actor;
+        return ps;
+    };
+    OutView o2v;
+    if (out_ba) o2v = view(out_ba);
+    rc = hip_err(launch_delta_pair(side(a, a_tombs, a_doc_actor, a_actor), side(bs, b->tombs, b->doc_actor, b->actor),
+                                   view(out_ab), out_ba ? &o2v : nullptr, kind_ab, kind_ba, make_work(ctx),
+                                   block_grid(ctx), s));
+    return leave(ctx, s, cap, rc);
+}
+
+int crdt_awset_delta_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
+                                const crdt_awset_out* out, uint8_t* kind, void* stream) {
+    return delta_pair_common(ctx, dst, nullptr, nullptr, 0u, src, out, nullptr, kind, nullptr, stream);
+}
+
+int crdt_awset_delta_exchange_async(crdt_ctx* ctx, const crdt_replica* a, const crdt_replica* b,
+                                    const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
+                                    uint8_t* kind_ba, void* stream) {
+    if (!a || !out_ba) return CRDT_E_INVALID;
+    return delta_pair_common(ctx, a->state, a->tombs, a->doc_actor, a->actor, b, out_ab, out_ba, kind_ab, kind_ba,
+                             stream);
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,

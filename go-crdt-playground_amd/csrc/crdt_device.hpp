@@ -149,6 +149,15 @@ struct TombView {  // AWSetDelta.Deleted of each doc (NULL offsets: none)
     const uint64_t* counters;
 };
 
+// One resident replica as the pair kernels read it (delta_pair.hip; crdt_replica
+// flattened into the kernel arguments).
+struct PairSide {
+    BatchView st;
+    TombView tb;  // offsets == NULL: no tombstones
+    const uint32_t* doc_actor;  // NULL: `actor` for every document
+    uint32_t actor;
+};
+
 struct TombOut {
     uint32_t* offsets;
     uint32_t* counts;

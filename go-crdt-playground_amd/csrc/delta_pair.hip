@@ -1,0 +1,313 @@
+// Delta-state merge of a resident replica pair: out_ab[d] = a[d] <- b[d] and
+// (exchange) out_ba[d] = b[d] <- a[d], each one (*AWSetDelta).Merge
+// (awset-delta_test.go:51-65), from one read of both replicas.  The replicas
+// stay in the shape apply, scatter, the joins and the folds write (state,
+// Deleted, actor): no packed source batch is built.
+//
+// A direction dst <- src of one document, s = src's actor, D / S the clocks as
+// they were before the call:
+//   FULL   D.Counter(s) == 0 (:53): merge(S, src.Entries), tombstones ignored
+//   DELTA  otherwise, when some src entry has a dot D has not seen (changed,
+//          :84-92) or some src tombstone passes the re-add filter (:93-102):
+//          deltaMerge (:107-166), clock max(D, S)
+//   NONE   otherwise (:60): dst's live entries and dst's clock, unchanged
+// The per-key rule of FULL and DELTA is decide() of merge_block.hpp.
+//
+// Two paths, one launch each:
+//  * delta_pair_wave_kernel: one wavefront per document when both sides hold
+//    <= 64 live entries and <= 64 live tombstones.  Both entry lists, both
+//    tombstone lists and both clocks are staged in LDS once and both directions
+//    are decided from that staging.  Lane i owns entry i of each side; a lookup
+//    on the other side is an LDS binary search.  The kind of a direction is
+//    taken first (Counter, then a ballot over changed and over the effective
+//    tombstones); then every lane decides its two keys and the survivors are
+//    compacted by ballot and popcount, as in join_wave_kernel, so the output is
+//    sorted by key and written once.  Larger documents go to the worklist.
+//  * delta_pair_block_kernel: workgroups pop the worklist; per direction one
+//    pass over src's entries and tombstones takes the kind, then block_merge
+//    runs in full or delta mode, or dst is copied for NONE.
+#include "crdt_device.hpp"
+#include "merge_block.hpp"
+
+namespace crdt {
+
+constexpr int kPairWaves = 4;      // wavefronts (= documents) per workgroup of the wave path
+constexpr int kPairWaveMax = 64;   // live entries, and live tombstones, per side the wave path takes
+constexpr int kPairBlockNT = 256;  // block path: threads per workgroup
+constexpr int kPairBlockIPT = 4;   // block path: merged positions per thread and window
+
+// Live prefix of document d of a five-array list: its first slot in o0, its
+// length returned, clamped to the document's slots (kErrCapacity).
+__device__ __forceinline__ uint32_t pair_live(const uint32_t* offsets, const uint32_t* counts, uint32_t d,
+                                              uint32_t& o0, uint32_t& err) {
+    o0 = offsets[d];
+    const uint32_t slots = offsets[d + 1] - o0;
+    uint32_t n = counts ? counts[d] : slots;
+    if (n > slots) {
+        n = slots;
+        err |= kErrCapacity;
+    }
+    return n;
+}
+
+// Per wave: index 0 = replica a, 1 = replica b.
+struct PairWaveSmem {
+    uint64_t ek[2][64], ec[2][64];  // entries
+    uint64_t tk[2][64], tc[2][64];  // tombstones
+    uint64_t vv[2][64];
+    uint32_t ea[2][64], ta[2][64];
+};
+
+// One direction of a wave-path document: dst = side x of sm, src = side 1 - x.
+__device__ __forceinline__ void pair_wave_dir(const PairWaveSmem& sm, uint32_t x, uint32_t nd, uint32_t ns,
+                                              uint32_t nts, uint32_t s_actor, uint32_t R, uint32_t d,
+                                              uint32_t obase, const OutView& out, uint8_t* kind_out, uint32_t lane,
+                                              uint32_t& err) {
+    const uint32_t y = 1u - x;
+    const uint64_t* const dk = sm.ek[x];
+    const uint64_t* const sk = sm.ek[y];
+    const uint64_t* const dvv = sm.vv[x];
+    const uint64_t* const svv = sm.vv[y];
+    const Entries tomb{sm.tk[y], sm.ta[y], sm.tc[y], nts};
+    const bool dv = lane < nd, sv = lane < ns, tv = lane < nts;
+    const uint64_t Dk = dk[lane], Dc = sm.ec[x][lane], Sk = sk[lane], Sc = sm.ec[y][lane];
+    const uint32_t Da = sm.ea[x][lane], Sa = sm.ea[y][lane];
+
+    // the kind, before any entry is decided (:53, :60)
+    const bool full = uniform((uint32_t)(vv_counter(dvv, R, s_actor, err) == 0ull)) != 0u;
+    uint32_t kind = CRDT_DELTA_FULL;
+    if (!full) {
+        const bool changed = sv && !has_dot(dvv, R, Sa, Sc, err);
+        bool effective = false;  // a tombstone the re-add filter lets through (:93-102)
+        if (tv) {
+            const uint64_t Tk = sm.tk[y][lane];
+            const uint32_t m = lower_bound_pow<6>(sk, ns, Tk);
+            const bool readded = m < ns && sk[m & 63] == Tk &&
+                                 (sm.ea[y][m & 63] != sm.ta[y][lane] || sm.ec[y][m & 63] > sm.tc[y][lane]);
+            effective = !readded;
+        }
+        kind = (ballot(changed) | ballot(effective)) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
+    }
+
+    // # src keys < Dk, # dst keys < Sk
+    const uint32_t j = lower_bound_pow<6>(sk, ns, Dk);
+    const uint32_t i = lower_bound_pow<6>(dk, nd, Sk);
+    const bool dmatch = dv && j < ns && sk[j & 63] == Dk;
+    const bool smatch = sv && i < nd && dk[i & 63] == Sk;
+    bool dkeep = false, skeep = false;
+    uint32_t oda = Da, osa = Sa;
+    uint64_t odc = Dc, osc = Sc;
+    if (kind == CRDT_DELTA_NONE) {
+        dkeep = dv;
+    } else {
+        if (dv)
+            dkeep = decide(true, Da, Dc, dmatch, dmatch ? sm.ea[y][j & 63] : 0u, dmatch ? sm.ec[y][j & 63] : 0ull, full,
+                           dvv, svv, R, tomb, Dk, oda, odc, err);
+        if (sv && !smatch) skeep = decide(false, 0u, 0ull, true, Sa, Sc, full, dvv, svv, R, tomb, Sk, osa, osc, err);
+    }
+    // a survivor's slot: kept lanes of its own side below it + kept entries of
+    // the other side with a smaller key
+    const uint64_t dm = ballot(dkeep), smk = ballot(skeep);
+    const uint32_t dpos = below(dm) + popc(smk & low_mask(j));
+    const uint32_t spos = below(smk) + popc(dm & low_mask(i));
+    const uint32_t n_out = popc(dm) + popc(smk);  // <= nd + ns <= the document's output slots
+    if (dkeep) {
+        out.keys[obase + dpos] = Dk;
+        out.actors[obase + dpos] = oda;
+        out.counters[obase + dpos] = odc;
+    }
+    if (skeep) {
+        out.keys[obase + spos] = Sk;
+        out.actors[obase + spos] = osa;
+        out.counters[obase + spos] = osc;
+    }
+    if (lane == 0) {
+        out.counts[d] = n_out;
+        if (kind_out) kind_out[d] = (uint8_t)kind;
+    }
+    if (lane < R) {
+        const uint64_t a = dvv[lane], b = svv[lane];
+        out.vv[(size_t)d * R + lane] = (kind == CRDT_DELTA_NONE || a > b) ? a : b;  // (:165; NONE: untouched)
+    }
+}
+
+// EXCH: also out_ba = b <- a.  Without it a's tombstones are never read (A.tb is empty).
+template <int WAVES, bool EXCH>
+__global__ __launch_bounds__(WAVES * 64) void delta_pair_wave_kernel(PairSide A, PairSide B, OutView o_ab,
+                                                                     OutView o_ba, uint8_t* kind_ab, uint8_t* kind_ba,
+                                                                     Work wk) {
+    __shared__ PairWaveSmem smem[WAVES];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t R = A.st.R, n_docs = A.st.n_docs;
+    const uint32_t d = uniform(blockIdx.x * WAVES + w);
+    if (d >= n_docs) return;  // (a whole wave; the kernel has no workgroup barrier)
+    PairWaveSmem& sm = smem[w];
+    uint32_t err = 0;
+
+    uint32_t ao, bo, ato = 0, bto = 0;
+    const uint32_t na = pair_live(A.st.offsets, A.st.counts, d, ao, err);
+    const uint32_t nb = pair_live(B.st.offsets, B.st.counts, d, bo, err);
+    const uint32_t nta = (EXCH && A.tb.offsets) ? pair_live(A.tb.offsets, A.tb.counts, d, ato, err) : 0u;
+    const uint32_t ntb = B.tb.offsets ? pair_live(B.tb.offsets, B.tb.counts, d, bto, err) : 0u;
+    const uint32_t obase = ao + bo;
+
+    // slot bounds: every document, whichever path merges it
+    if (lane == 0) {
+        o_ab.offsets[d] = obase;
+        if (EXCH) o_ba.offsets[d] = obase;
+        if (d == n_docs - 1) {
+            const uint32_t end_off = A.st.offsets[n_docs] + B.st.offsets[n_docs];
+            o_ab.offsets[n_docs] = end_off;
+            if (EXCH) o_ba.offsets[n_docs] = end_off;
+        }
+    }
+    if (na > kPairWaveMax || nb > kPairWaveMax || nta > kPairWaveMax || ntb > kPairWaveMax) {
+        if (lane == 0) push_work(wk, d, n_docs);
+        flag_error(wk.status, err);
+        return;
+    }
+
+    // both replicas' document, once
+    if (lane < na) {
+        sm.ek[0][lane] = A.st.keys[ao + lane];
+        sm.ea[0][lane] = A.st.actors[ao + lane];
+        sm.ec[0][lane] = A.st.counters[ao + lane];
+    }
+    if (lane < nb) {
+        sm.ek[1][lane] = B.st.keys[bo + lane];
+        sm.ea[1][lane] = B.st.actors[bo + lane];
+        sm.ec[1][lane] = B.st.counters[bo + lane];
+    }
+    if (lane < nta) {
+        sm.tk[0][lane] = A.tb.keys[ato + lane];
+        sm.ta[0][lane] = A.tb.actors[ato + lane];
+        sm.tc[0][lane] = A.tb.counters[ato + lane];
+    }
+    if (lane < ntb) {
+        sm.tk[1][lane] = B.tb.keys[bto + lane];
+        sm.ta[1][lane] = B.tb.actors[bto + lane];
+        sm.tc[1][lane] = B.tb.counters[bto + lane];
+    }
+    if (lane < R) {
+        sm.vv[0][lane] = A.st.vv[(size_t)d * R + lane];
+        sm.vv[1][lane] = B.st.vv[(size_t)d * R + lane];
+    }
+    wave_sync();
+
+    const uint32_t b_actor = B.doc_actor ? B.doc_actor[d] : B.actor;
+    pair_wave_dir(sm, 0u, na, nb, ntb, b_actor, R, d, obase, o_ab, kind_ab, lane, err);
+    if (EXCH) {
+        const uint32_t a_actor = A.doc_actor ? A.doc_actor[d] : A.actor;
+        pair_wave_dir(sm, 1u, nb, na, nta, a_actor, R, d, obase, o_ba, kind_ba, lane, err);
+    }
+    flag_error(wk.status, err);
+}
+
+// One direction of a block-path document, by the whole workgroup.
+template <int NT, int IPT>
+__device__ void pair_block_dir(const PairSide& Dd, const PairSide& Sd, uint32_t d, uint32_t R,
+                               MergeSmem<NT, IPT>& sm, const OutView& out, uint8_t* kind_out, uint32_t& err) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t doff, soff, toff = 0;
+    const uint32_t nd = pair_live(Dd.st.offsets, Dd.st.counts, d, doff, err);
+    const uint32_t ns = pair_live(Sd.st.offsets, Sd.st.counts, d, soff, err);
+    const uint32_t nt = Sd.tb.offsets ? pair_live(Sd.tb.offsets, Sd.tb.counts, d, toff, err) : 0u;
+    const Entries D{Dd.st.keys + doff, Dd.st.actors + doff, Dd.st.counters + doff, nd};
+    const Entries S{Sd.st.keys + soff, Sd.st.actors + soff, Sd.st.counters + soff, ns};
+    const Entries T{nt ? Sd.tb.keys + toff : nullptr, nt ? Sd.tb.actors + toff : nullptr,
+                    nt ? Sd.tb.counters + toff : nullptr, nt};
+    if (tid < R) {
+        sm.dvv[tid] = Dd.st.vv[(size_t)d * R + tid];
+        sm.svv[tid] = Sd.st.vv[(size_t)d * R + tid];
+    }
+    __syncthreads();
+    const uint32_t s_actor = Sd.doc_actor ? Sd.doc_actor[d] : Sd.actor;
+    const bool full = vv_counter(sm.dvv, R, s_actor, err) == 0ull;  // (every thread reads the same words)
+    uint32_t kind = CRDT_DELTA_FULL;
+    if (!full) {
+        bool any = false;
+        for (uint32_t t = tid; t < ns; t += NT) any |= !has_dot(sm.dvv, R, S.a[t], S.c[t], err);  // changed, :84-92
+        for (uint32_t t = tid; t < nt; t += NT) {  // the re-add filter, :93-102
+            uint32_t ea;
+            uint64_t ec;
+            const bool readded = tomb_find(S, T.k[t], ea, ec) && (ea != T.a[t] || ec > T.c[t]);
+            any |= !readded;
+        }
+        kind = __syncthreads_or(any) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
+    }
+    const uint32_t obase = Dd.st.offsets[d] + Sd.st.offsets[d];
+    const EntriesOut O{out.keys + obase, out.actors + obase, out.counters + obase};
+    uint32_t n;
+    if (kind == CRDT_DELTA_NONE) {
+        for (uint32_t t = tid; t < nd; t += NT) {
+            O.k[t] = D.k[t];
+            O.a[t] = D.a[t];
+            O.c[t] = D.c[t];
+        }
+        n = nd;
+    } else {
+        n = block_merge<NT, IPT>(D, S, T, full, R, sm, O, err);
+    }
+    if (tid == 0) {
+        out.counts[d] = n;
+        if (kind_out) kind_out[d] = (uint8_t)kind;
+    }
+    if (tid < R) {
+        const uint64_t a = sm.dvv[tid], b = sm.svv[tid];
+        out.vv[(size_t)d * R + tid] = (kind == CRDT_DELTA_NONE || a > b) ? a : b;
+    }
+    __syncthreads();  // sm.dvv / sm.svv are the next direction's
+}
+
+template <int NT, int IPT, bool EXCH>
+__global__ __launch_bounds__(NT) void delta_pair_block_kernel(PairSide A, PairSide B, OutView o_ab, OutView o_ba,
+                                                              uint8_t* kind_ab, uint8_t* kind_ba, Work wk) {
+    __shared__ MergeSmem<NT, IPT> sm;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t R = A.st.R, n_docs = A.st.n_docs;
+    uint32_t err = 0;
+    if (work_total(wk, n_docs) == 0) return;  // empty worklist (set by the previous launch)
+    for (;;) {
+        if (tid == 0) sm.word[0] = atomicAdd(wk.wl_head, 1u);
+        __syncthreads();
+        const uint32_t slot = sm.word[0];
+        const uint32_t total = work_total(wk, n_docs);
+        __syncthreads();
+        if (slot >= total) break;
+        const uint32_t d = wk.worklist[slot];
+        if (d >= n_docs) {  // not a document of this call: never dereferenced
+            if (tid == 0) atomicOr(wk.status, kErrWorkspace);
+            continue;
+        }
+        pair_block_dir<NT, IPT>(A, B, d, R, sm, o_ab, kind_ab, err);
+        if (EXCH) pair_block_dir<NT, IPT>(B, A, d, R, sm, o_ba, kind_ba, err);
+    }
+    flag_error(wk.status, err);
+}
+
+// out_ba == nullptr: the join (one direction, a's tombstones unused).
+hipError_t launch_delta_pair(const PairSide& A, const PairSide& B, const OutView& out_ab, const OutView* out_ba,
+                             uint8_t* kind_ab, uint8_t* kind_ba, const Work& wk, uint32_t block_grid,
+                             hipStream_t stream) {
+    const uint32_t n = A.st.n_docs;
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + kPairWaves - 1) / kPairWaves), block(kPairWaves * 64);
+    if (out_ba)
+        hipLaunchKernelGGL((delta_pair_wave_kernel<kPairWaves, true>), grid, block, 0, stream, A, B, out_ab, *out_ba,
+                           kind_ab, kind_ba, wk);
+    else
+        hipLaunchKernelGGL((delta_pair_wave_kernel<kPairWaves, false>), grid, block, 0, stream, A, B, out_ab, out_ab,
+                           kind_ab, kind_ba, wk);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (out_ba)
+        hipLaunchKernelGGL((delta_pair_block_kernel<kPairBlockNT, kPairBlockIPT, true>), dim3(block_grid),
+                           dim3(kPairBlockNT), 0, stream, A, B, out_ab, *out_ba, kind_ab, kind_ba, wk);
+    else
+        hipLaunchKernelGGL((delta_pair_block_kernel<kPairBlockNT, kPairBlockIPT, false>), dim3(block_grid),
+                           dim3(kPairBlockNT), 0, stream, A, B, out_ab, out_ab, kind_ab, kind_ba, wk);
+    return hipGetLastError();
+}
+
+}  // namespace crdt

@@ -52,6 +52,10 @@
  *       P resident replicas of every document gathered into the packed source
  *       batch the folds and the delta extraction read (no reference
  *       counterpart: the reference folds replicas it holds as Go values)
+ *   crdt_awset_delta_join_async / crdt_awset_delta_exchange_async
+ *       replace (*AWSetDelta).Merge, and the pair A.Merge(B); B.Merge(A) of
+ *       the reference's own test, on resident replicas as they stand
+ *                                      awset-delta_test.go:51-166, 173-174
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -776,6 +780,55 @@ typedef struct {                     /* one resident replica of every document (
 } crdt_replica;
 int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n_reps, uint32_t entry_slots,
                              uint32_t tomb_slots, const crdt_delta_out* out, void* stream);
+
+/* ---- delta merge of a resident replica pair ---------------------------------
+ * (*AWSetDelta).Merge (awset-delta_test.go:51-65) applied to replicas in their
+ * resident shape, with no source batch in between: out[d] = dst[d] <- src[d],
+ * and for the exchange out_ab[d] = a[d] <- b[d] AND out_ba[d] = b[d] <- a[d]
+ * (the test's A.Merge(B); B.Merge(A), :173-174) from ONE read of both replicas;
+ * both directions read the states as they were before the call.  A crdt_replica
+ * is used as it stands (state, tombs or NULL, doc_actor or actor); the join's
+ * dst is a plain state, since the destination's tombstones and actor are not read.
+ * Per direction dst <- src of document d, with s = src's actor for d and D, S
+ * the two clocks before the call, kind[d] (when kind != NULL) is
+ *   CRDT_DELTA_FULL   D.Counter(s) == 0 (:53): merge(S, src.Entries), exactly
+ *                     what crdt_awset_join_async writes; tombstones ignored
+ *   CRDT_DELTA_NONE   otherwise, when no src entry has a dot D has not seen
+ *                     (changed, :84-92) and no src tombstone passes the re-add
+ *                     filter (:93-102, which reads src's own entries, not D):
+ *                     dst's live entries and dst's clock UNCHANGED (:60: the
+ *                     clock is not merged)
+ *   CRDT_DELTA_DELTA  otherwise: deltaMerge (:107-166).  Phase 2 runs over the
+ *                     entries after phase 1, so an entry phase 1 just added can
+ *                     be removed by a tombstone of its key; a tombstone whose key
+ *                     neither replica holds still makes the document DELTA; the
+ *                     clock becomes max(D, S).
+ * Layout: the join's.  Document d of either output is at a.offsets[d] +
+ * b.offsets[d] with both inputs' capacity, entries in key order; offsets, counts
+ * and vv are written for every document; slack is unspecified.  Only live
+ * prefixes are read (counts, or all slots when counts == NULL), of entries and
+ * tombstones alike; the two replicas' slot layouts are independent; any join,
+ * exchange, fold, apply, select or scatter output is a valid state as it stands.
+ * Reported by crdt_ctx_sync:
+ *   CRDT_E_ACTOR_RANGE  Counter(s) at s == R, and any HasDot the chosen path
+ *                       evaluates at actor == R (as in the folds); s > R is
+ *                       "never seen": the document is FULL
+ *   CRDT_E_CAPACITY     a live count above its slots (clamped)
+ * Returned by the call (CRDT_E_INVALID): a NULL argument other than kind; an
+ * n_docs or R mismatch; R out of range; a tomb batch without offsets; two output
+ * arrays starting at one address (the key sets of the two directions differ:
+ * there is no shared key column) or overlapping per-document arrays; an output
+ * array starting where an input array of the same kind starts.
+ * n_docs == 0 launches nothing.  Ordered after the context's previous call; no
+ * host sync, kernel nodes only, capturable.  Workspace: the join's worklist, one
+ * word per document, sized by crdt_ctx_reserve(max_docs, ..); CRDT_E_WORKSPACE
+ * when it would have to grow during a graph capture.  There is no _batch form: a
+ * caller who holds host data builds a source batch and folds. */
+int crdt_awset_delta_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
+                                const crdt_awset_out* out, uint8_t* kind /* [n_docs] or NULL */, void* stream);
+int crdt_awset_delta_exchange_async(crdt_ctx* ctx, const crdt_replica* a, const crdt_replica* b,
+                                    const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
+                                    uint8_t* kind_ab, uint8_t* kind_ba /* each [n_docs] or NULL */, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
