@@ -128,6 +128,10 @@ class CReplica(ctypes.Structure):
     _fields_ = [("state", _vp), ("tombs", _vp), ("doc_actor", _vp), ("actor", _u32)]
 
 
+class CReplicaOut(ctypes.Structure):
+    _fields_ = [("state", _vp), ("tombs", _vp), ("doc_actor", _vp)]
+
+
 class CrdtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -215,6 +219,9 @@ def signatures():
         "crdt_awset_delta_join_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CReplica), P(CAWSetOut), _vp, _vp]),
         "crdt_awset_delta_exchange_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), P(CAWSetOut), P(CAWSetOut),
                                                            _vp, _vp, _vp]),
+        "crdt_replica_select_async": (ctypes.c_int, [_vp, P(CReplica), _vp, _vp, _u32, _u32, _u32, P(CReplicaOut), _vp]),
+        "crdt_replica_scatter_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), _vp, _vp, _u32, _u32,
+                                                      P(CReplicaOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CSrcBatch,
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaOut, CSrcBatch,
                   CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -390,6 +390,58 @@ class Replica:
     def to(self, device) -> "Replica":
         return Replica(self.state.to(device), self.tombs.to(device) if self.tombs is not None else None,
                        self.actor, _torch(self.doc_actor, device))
+
+
+class ReplicaBuffers:
+    """Storage a replica select / scatter writes (crdt_replica_out): the state
+    (OutBuffers of `entry_slots`), the tombstones (TombBuffers of `tomb_slots`;
+    tombs=False: none, for replicas without a Deleted map) and the per-document
+    actors (actors=False: not written).  numpy, or torch on `device`.
+    as_replica() hands the result back as the Replica of the next call."""
+
+    def __init__(self, n_docs, R, entry_slots, tomb_slots=0, device=None, tombs=True, actors=True):
+        self.n_docs, self.R = int(n_docs), int(R)
+        self.entry_slots, self.tomb_slots = int(entry_slots), int(tomb_slots) if tombs else 0
+        self.state = OutBuffers(n_docs, R, entry_slots, device=device)
+        self.tombs = TombBuffers(n_docs, tomb_slots, device=device) if tombs else None
+        if not actors:
+            self.doc_actor = None
+        elif device is None:
+            self.doc_actor = np.zeros(max(n_docs, 1), U32)[:n_docs]
+        else:
+            import torch
+
+            self.doc_actor = torch.empty(max(n_docs, 1), dtype=torch.int32, device=device)[:n_docs]
+
+    def c(self) -> CReplicaOut:
+        cs = self.state.c()
+        ct = self.tombs.c_out() if self.tombs is not None else None
+        r = CReplicaOut(ctypes.addressof(cs), ctypes.addressof(ct) if ct is not None else None, ptr(self.doc_actor))
+        r._keep = (cs, ct)  # the structs the descriptor points at live as long as it does
+        return r
+
+    def as_replica(self, actor: int = 0) -> "Replica":
+        """The written replica as an input: its state with counts, its tombstones with
+        counts, and its actors (`actor` for every document when they were not written)."""
+        return Replica(self.state.as_batch(), self.tombs, actor, self.doc_actor)
+
+    def numpy(self) -> "Replica":
+        """Host copy trimmed to the packed totals (offsets[n_docs] of entries and tombstones,
+        each at most its slots)."""
+        n, R = self.n_docs, self.R
+        off = _np(self.state.offsets, U32)[: n + 1]
+        te = min(int(off[n]), self.entry_slots)
+        st = AWSetBatch(R, off, _np(self.state.keys, U64)[:te], _np(self.state.actors, U32)[:te],
+                        _np(self.state.counters, U64)[:te], _np(self.state.vv, U64)[: n * R],
+                        counts=_np(self.state.counts, U32)[:n])
+        tb = None
+        if self.tombs is not None:
+            toff = _np(self.tombs.offsets, U32)[: n + 1]
+            tt = min(int(toff[n]), self.tomb_slots)
+            tb = TombBatch(toff, _np(self.tombs.keys, U64)[:tt], _np(self.tombs.actors, U32)[:tt],
+                           _np(self.tombs.counters, U64)[:tt], counts=_np(self.tombs.counts, U32)[:n])
+        da = None if self.doc_actor is None else _np(self.doc_actor, U32)[:n]
+        return Replica(st, tb, 0, da)
 
 
 class QueryBatch:

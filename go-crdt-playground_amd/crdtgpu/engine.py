@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, ReplicaBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -303,6 +303,80 @@ class Engine:
             h.keys, h.actors, h.counters = _np(o.keys, np.uint64), _np(o.actors, np.uint32), _np(o.counters, np.uint64)
             host.append(h)
         return host[0], host[1], _np(kinds[0], np.uint8)[:n], _np(kinds[1], np.uint8)[:n]
+
+    def replica_select_async(self, rep, out: ReplicaBuffers, idx=None, n_idx=None, n_out=None, entry_slots=None,
+                             tomb_slots=None, stream=None):
+        """select_async over a whole resident Replica: out doc j = rep doc idx[j] for
+        j < *n_idx (live entries, count, VV, live tombstones, actor), empty beyond, entries
+        and tombstones each packed with no slack (crdt_replica_select_async).  idx / n_idx:
+        device u32 arrays (a worklist / n_work); all None: compaction of the replica.  The
+        slot limits default to the sizes out was made with."""
+        cr, co = _c(rep), _c(out)
+        n_out = out.n_docs if n_out is None else n_out
+        entry_slots = out.entry_slots if entry_slots is None else entry_slots
+        tomb_slots = out.tomb_slots if tomb_slots is None else tomb_slots
+        check(self._lib.crdt_replica_select_async(self._ctx, ctypes.byref(cr), ptr(idx), ptr(n_idx), int(n_out),
+                                                  int(entry_slots), int(tomb_slots), ctypes.byref(co),
+                                                  _stream(stream)), "crdt_replica_select_async")
+
+    def replica_scatter_async(self, rep, sub, idx, out: ReplicaBuffers, n_idx=None, entry_slots=None,
+                              tomb_slots=None, stream=None):
+        """scatter_async over whole resident Replicas: out doc d = sub doc j when
+        idx[j] == d for some j < *n_idx, else rep doc d, with its tombstones and actor
+        (crdt_replica_scatter_async).  sub is typically a delta exchange's or an apply's
+        output over the selected sub-replica, with the selected tombstones and actors."""
+        cr, cs, co = _c(rep), _c(sub), _c(out)
+        entry_slots = out.entry_slots if entry_slots is None else entry_slots
+        tomb_slots = out.tomb_slots if tomb_slots is None else tomb_slots
+        check(self._lib.crdt_replica_scatter_async(self._ctx, ctypes.byref(cr), ctypes.byref(cs), ptr(idx),
+                                                   ptr(n_idx), int(entry_slots), int(tomb_slots), ctypes.byref(co),
+                                                   _stream(stream)), "crdt_replica_scatter_async")
+
+    @staticmethod
+    def _tomb_live(rep) -> int:
+        if rep.tombs is None:
+            return 0
+        if rep.tombs.counts is not None:
+            return int(rep.tombs.counts.astype("uint64").sum())
+        return int(rep.tombs.offsets[-1]) - int(rep.tombs.offsets[0])
+
+    def replica_select(self, rep, idx=None, n_idx=None, n_out=None):
+        """Host Replica uploaded, selected on the device and downloaded as a Replica trimmed
+        to its packed sizes (for tests and small callers).  idx: host u32 array or None;
+        n_idx: int or None."""
+        import numpy as np
+        import torch
+
+        rep = rep.numpy()
+        dev = torch.device("cuda", self.device)
+        n_out = (rep.n_docs if idx is None else len(idx)) if n_out is None else int(n_out)
+        reps = max(1, -(-n_out // max(rep.n_docs, 1)))  # an idx that repeats may select a document many times
+        out = ReplicaBuffers(n_out, rep.state.R, rep.state.live_slots() * reps, self._tomb_live(rep) * reps,
+                             device=dev, tombs=rep.tombs is not None)
+        didx = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, np.uint32).view(np.int32)).to(dev)
+        dn = None if n_idx is None else torch.tensor([int(n_idx)], dtype=torch.int32, device=dev)
+        self.replica_select_async(rep.to(dev), out, didx, dn)
+        self.sync()
+        return out.numpy()
+
+    def replica_scatter(self, rep, sub, idx, n_idx=None):
+        """Host Replicas uploaded, scattered on the device and downloaded as a Replica
+        trimmed to its packed sizes (for tests and small callers)."""
+        import numpy as np
+        import torch
+
+        rep, sub = rep.numpy(), sub.numpy()
+        dev = torch.device("cuda", self.device)
+        out = ReplicaBuffers(rep.n_docs, rep.state.R, rep.state.live_slots() + sub.state.live_slots(),
+                             self._tomb_live(rep) + self._tomb_live(sub), device=dev,
+                             tombs=rep.tombs is not None or sub.tombs is not None)
+        didx = torch.from_numpy(np.ascontiguousarray(idx, np.uint32).view(np.int32)).to(dev)
+        if didx.numel() == 0:
+            didx = torch.zeros(1, dtype=torch.int32, device=dev)
+        dn = None if n_idx is None else torch.tensor([int(n_idx)], dtype=torch.int32, device=dev)
+        self.replica_scatter_async(rep.to(dev), sub.to(dev), didx, out, dn)
+        self.sync()
+        return out.numpy()
 
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),

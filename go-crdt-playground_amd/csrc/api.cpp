@@ -58,6 +58,8 @@ hipError_t launch_diff(const BatchView& before, const BatchView& after, uint32_t
                        uint32_t n_cu, hipStream_t stream);
 hipError_t launch_sources(const SourcesArgs& s, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status, uint32_t n_cu,
                           hipStream_t stream);
+hipError_t launch_replica(const ReplicaArgs& a, uint32_t* inv, uint32_t* parts_e, uint32_t* parts_t, uint32_t* status,
+                          uint32_t n_cu, hipStream_t stream);
 hipError_t launch_delta_pair(const PairSide& A, const PairSide& B, const OutView& out_ab, const OutView* out_ba,
                              uint8_t* kind_ab, uint8_t* kind_ba, const Work& wk, uint32_t block_grid,
                              hipStream_t stream);
@@ -307,8 +309,9 @@ int grow(DevBuf& b, size_t want, bool capturing) {
 }
 
 int reserve_worklist(crdt_ctx* ctx, uint32_t n_docs) {
-    int rc = ctx->worklist.reserve(std::max<size_t>((size_t)n_docs, 1) * sizeof(uint32_t));
-    if (rc == CRDT_OK) rc = ctx->defer.reserve(std::max<size_t>((size_t)n_docs, 1) * sizeof(uint32_t));
+    // (two words at least: the replica scatter's two partial sums of a one-document replica)
+    int rc = ctx->worklist.reserve(std::max<size_t>((size_t)n_docs, 2) * sizeof(uint32_t));
+    if (rc == CRDT_OK) rc = ctx->defer.reserve(std::max<size_t>((size_t)n_docs, 2) * sizeof(uint32_t));
     return rc;
 }
 
@@ -937,6 +940,112 @@ int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n
     rc = hip_err(launch_sources(a, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(), make_work(ctx).status,
                                 (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
+}
+
+// Replica select / scatter (replica.hip).  sub == NULL: the select.  The scan's
+// partial sums are one word per 1,024 output documents for the entries and one
+// for the tombstones.  Select keeps them in the worklist and the defer buffer;
+// scatter keeps its inverse map (one word per document) in the worklist buffer
+// and both partial arrays in the defer buffer (2 * ceil(n / 1,024) <= max(n, 2)
+// words), which is what crdt_ctx_reserve(max_docs, ..) sizes them for.
+static int replica_common(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
+                          const uint32_t* n_idx, uint32_t n_out, uint32_t entry_slots, uint32_t tomb_slots,
+                          const crdt_replica_out* out, bool scatter, void* stream) {
+    if (!ctx || !rep || !batch_ptrs_ok(rep->state) || !out || !out_ptrs_ok(out->state)) return CRDT_E_INVALID;
+    if (scatter && (!sub || !batch_ptrs_ok(sub->state) || !idx || sub->state->R != rep->state->R))
+        return CRDT_E_INVALID;
+    const crdt_replica* in[2] = {rep, scatter ? sub : nullptr};
+    const crdt_awset_out* os = out->state;
+    const crdt_tomb_out* ot = out->tombs;
+    bool any_t = false;
+    for (const crdt_replica* r : in) {
+        if (!r) continue;
+        const crdt_awset_batch* b = r->state;
+        const crdt_tomb_batch* t = r->tombs;
+        if (t) {
+            if (!t->offsets) return CRDT_E_INVALID;
+            any_t = true;
+        }
+        // no output array starts where an input array of the same kind starts
+        const uint32_t* in32[] = {b->offsets, b->counts, b->actors, r->doc_actor, t ? t->offsets : nullptr,
+                                  t ? t->counts : nullptr, t ? t->actors : nullptr};
+        const uint64_t* in64[] = {b->keys, b->counters, b->vv, t ? t->keys : nullptr, t ? t->counters : nullptr};
+        const uint32_t* out32[] = {os->offsets, os->counts, os->actors, out->doc_actor, ot ? ot->offsets : nullptr,
+                                   ot ? ot->counts : nullptr, ot ? ot->actors : nullptr};
+        const uint64_t* out64[] = {os->keys, os->counters, os->vv, ot ? ot->keys : nullptr, ot ? ot->counters : nullptr};
+        for (const uint32_t* o : out32)
+            for (const uint32_t* i : in32)
+                if (o && o == i) return CRDT_E_INVALID;
+        for (const uint64_t* o : out64)
+            for (const uint64_t* i : in64)
+                if (o && o == i) return CRDT_E_INVALID;
+    }
+    if (any_t && (!ot || !ot->offsets || !ot->counts || !ot->keys || !ot->actors || !ot->counters))
+        return CRDT_E_INVALID;
+    auto side = [](const crdt_replica* r) {
+        RepSide s{};
+        const crdt_awset_batch* b = r->state;
+        s.n_docs = b->n_docs;
+        s.actor = r->actor;
+        s.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
+        if (const crdt_tomb_batch* t = r->tombs) s.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
+        s.vv = b->vv;
+        s.doc_actor = r->doc_actor;
+        return s;
+    };
+    ReplicaArgs a{};
+    a.rep = side(rep);
+    if (scatter) a.sub = side(sub);
+    a.idx = idx;
+    a.n_idx = n_idx;
+    // an empty call writes offsets[0] = 0 alone and launches nothing that reads documents
+    const uint32_t n = rep->state->n_docs == 0 ? 0u : (scatter ? rep->state->n_docs : n_out);
+    a.n_out = n;
+    a.R = rep->state->R;
+    a.entry_slots = entry_slots;
+    a.tomb_slots = tomb_slots;
+    a.out = view(os);
+    if (ot) {
+        a.tout = TombOut{ot->offsets, ot->counts, ot->keys, ot->actors, ot->counters};
+        if (!any_t) a.tout.keys = nullptr;  // offsets (and counts) zeroed, no column written
+    }
+    a.out_actor = out->doc_actor;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    const size_t n_parts = ((size_t)n + 1023) / 1024;
+    uint32_t *inv = nullptr, *parts_e = nullptr, *parts_t = nullptr;
+    if (scatter) {
+        if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n, 1) * sizeof(uint32_t), cap);
+        if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(2 * n_parts, 2) * sizeof(uint32_t), cap);
+        if (rc != CRDT_OK) return rc;
+        inv = ctx->worklist.as<uint32_t>();
+        parts_e = ctx->defer.as<uint32_t>();
+        parts_t = parts_e + n_parts;
+        a.inv = inv;
+    } else {
+        if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
+        if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
+        if (rc != CRDT_OK) return rc;
+        parts_e = ctx->worklist.as<uint32_t>();
+        parts_t = ctx->defer.as<uint32_t>();
+    }
+    rc = hip_err(launch_replica(a, inv, parts_e, parts_t, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+int crdt_replica_select_async(crdt_ctx* ctx, const crdt_replica* rep, const uint32_t* idx, const uint32_t* n_idx,
+                              uint32_t n_out, uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out,
+                              void* stream) {
+    return replica_common(ctx, rep, nullptr, idx, n_idx, n_out, entry_slots, tomb_slots, out, false, stream);
+}
+
+int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
+                               const uint32_t* n_idx, uint32_t entry_slots, uint32_t tomb_slots,
+                               const crdt_replica_out* out, void* stream) {
+    return replica_common(ctx, rep, sub, idx, n_idx, 0u, entry_slots, tomb_slots, out, true, stream);
 }
 
 // Delta merge of a resident pair (delta_pair.hip).  Workspace: the join's

@@ -166,6 +166,29 @@ struct TombOut {
     uint64_t* counters;
 };
 
+// Replica select and scatter (replica.hip): the descriptors travel by value in the
+// kernel arguments.
+// One input replica (crdt_replica flattened).
+struct RepSide {
+    uint32_t n_docs;
+    uint32_t actor;
+    SrcCols e, t;               // t.off == NULL: no tombstones
+    const uint64_t* vv;
+    const uint32_t* doc_actor;  // NULL: `actor` for every document
+};
+
+struct ReplicaArgs {
+    RepSide rep, sub;       // sub: scatter only
+    const uint32_t* idx;    // select: NULL = the identity; scatter: [sub.n_docs]
+    const uint32_t* n_idx;  // NULL: n_out (select) / sub.n_docs (scatter)
+    const uint32_t* inv;    // scatter: the inverse map; NULL: this is a select
+    uint32_t n_out, R;
+    uint32_t entry_slots, tomb_slots;
+    OutView out;
+    TombOut tout;         // offsets == NULL: not written; keys == NULL: only offsets and counts (zeros)
+    uint32_t* out_actor;  // NULL: not written
+};
+
 // Membership reads (query.hip): the five-array view both lookups read (an AWSet
 // batch without its clocks, or AWSetDelta.Deleted of each document), the
 // per-document query lists and the per-query outputs.

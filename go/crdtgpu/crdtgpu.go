@@ -16,6 +16,7 @@
 //	(*AWSetDelta).Merge  awset-delta_test.go:51-166  -> Engine.DeltaMerge / DeltaMergeBatch
 //	MakeDeltaMergeData   awset-delta_test.go:79-105  -> Engine.DeltaBatch (what to send a peer)
 //	resident replicas    (no reference counterpart)  -> Engine.SourcesBatch (fold / extraction input on the device)
+//	                                                    Engine.ReplicaSelect / ReplicaScatter (documents moved with Deleted and actors)
 //
 // AWSetDelta lives in a _test.go file of the reference, invisible to importers,
 // so this package defines it (with Del and Clone, awset-delta_test.go:9-49).
@@ -668,6 +669,102 @@ func (e *Engine) SourcesBatch(reps []Replica, entrySlots, tombSlots uint32, out 
 	if rc := C.crdt_awset_sources_async(e.ctx, &crs[0], C.uint32_t(len(reps)), C.uint32_t(entrySlots),
 		C.uint32_t(tombSlots), out, stream); rc != 0 {
 		return errOf("crdt_awset_sources_async", rc)
+	}
+	return nil
+}
+
+// ReplicaOut is the device storage a replica select or scatter writes: the state
+// (StateOut), the tombstones (Tombs, nil: none -- allowed only when no input replica
+// has Tombs) and one actor per output document (DocActor, nil: not written).
+// Every pointer is a device pointer.
+type ReplicaOut struct {
+	StateOut C.crdt_awset_out
+	Tombs    *C.crdt_tomb_out
+	DocActor *C.uint32_t
+}
+
+// replicaC lays a Replica out in C memory for the length of one call.
+func replicaC(a *arena, r *Replica) *C.crdt_replica {
+	pr := a.alloc(int(unsafe.Sizeof(C.crdt_replica{})))
+	ps := a.alloc(int(unsafe.Sizeof(C.crdt_awset_batch{})))
+	pt := a.alloc(int(unsafe.Sizeof(C.crdt_tomb_batch{})))
+	if a.err != nil {
+		return nil
+	}
+	st := (*C.crdt_awset_batch)(ps)
+	*st = r.State
+	cr := C.crdt_replica{state: st, doc_actor: r.DocActor, actor: C.uint32_t(r.Actor)}
+	if r.Tombs != nil {
+		tb := (*C.crdt_tomb_batch)(pt)
+		*tb = *r.Tombs
+		cr.tombs = tb
+	}
+	out := (*C.crdt_replica)(pr)
+	*out = cr
+	return out
+}
+
+// replicaOutC lays a ReplicaOut out in C memory for the length of one call.
+func replicaOutC(a *arena, o *ReplicaOut) *C.crdt_replica_out {
+	po := a.alloc(int(unsafe.Sizeof(C.crdt_replica_out{})))
+	ps := a.alloc(int(unsafe.Sizeof(C.crdt_awset_out{})))
+	pt := a.alloc(int(unsafe.Sizeof(C.crdt_tomb_out{})))
+	if a.err != nil {
+		return nil
+	}
+	st := (*C.crdt_awset_out)(ps)
+	*st = o.StateOut
+	co := C.crdt_replica_out{state: st, doc_actor: o.DocActor}
+	if o.Tombs != nil {
+		tb := (*C.crdt_tomb_out)(pt)
+		*tb = *o.Tombs
+		co.tombs = tb
+	}
+	out := (*C.crdt_replica_out)(po)
+	*out = co
+	return out
+}
+
+// ReplicaSelect gathers documents idx[0..*nIdx) of a resident replica (idx nil:
+// the identity; nIdx nil: nOut) into `out` on the device, with their
+// AWSetDelta.Deleted and their actors, entries and tombstones each packed with
+// no slack (crdt_replica_select_async). idx and nIdx are device pointers: a
+// compare or digest worklist and its n_work feed the call with nothing read
+// back. With idx and nIdx nil and nOut the replica's document count it compacts
+// the replica. Asynchronous on stream; device-side errors surface at the
+// context's next sync.
+func (e *Engine) ReplicaSelect(rep *Replica, idx, nIdx *C.uint32_t, nOut, entrySlots, tombSlots uint32,
+	out *ReplicaOut, stream unsafe.Pointer) error {
+	var a arena
+	defer a.free()
+	cr, co := replicaC(&a, rep), replicaOutC(&a, out)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_replica_select_async(e.ctx, cr, idx, nIdx, C.uint32_t(nOut), C.uint32_t(entrySlots),
+		C.uint32_t(tombSlots), co, stream); rc != 0 {
+		return errOf("crdt_replica_select_async", rc)
+	}
+	return nil
+}
+
+// ReplicaScatter puts a sub-replica back into the resident replica it was
+// selected from (crdt_replica_scatter_async): document d of out is sub's document
+// j when idx[j] == d for some j < *nIdx, and rep's document d otherwise, with its
+// tombstones and its actor. sub is typically the output of a delta exchange or an
+// apply over the selected documents. Asynchronous on stream; device-side errors
+// surface at the context's next sync.
+func (e *Engine) ReplicaScatter(rep, sub *Replica, idx, nIdx *C.uint32_t, entrySlots, tombSlots uint32,
+	out *ReplicaOut, stream unsafe.Pointer) error {
+	var a arena
+	defer a.free()
+	cr, cs, co := replicaC(&a, rep), replicaC(&a, sub), replicaOutC(&a, out)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_replica_scatter_async(e.ctx, cr, cs, idx, nIdx, C.uint32_t(entrySlots),
+		C.uint32_t(tombSlots), co, stream); rc != 0 {
+		return errOf("crdt_replica_scatter_async", rc)
 	}
 	return nil
 }

@@ -56,6 +56,10 @@
  *       replace (*AWSetDelta).Merge, and the pair A.Merge(B); B.Merge(A) of
  *       the reference's own test, on resident replicas as they stand
  *                                      awset-delta_test.go:51-166, 173-174
+ *   crdt_replica_select_async / crdt_replica_scatter_async
+ *       select and scatter over a whole replica: the documents move with
+ *       their Deleted tombstones and actors, which is what a sparse delta
+ *       round and a sparse apply need (no reference counterpart)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -780,6 +784,75 @@ typedef struct {                     /* one resident replica of every document (
 } crdt_replica;
 int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n_reps, uint32_t entry_slots,
                              uint32_t tomb_slots, const crdt_delta_out* out, void* stream);
+
+/* ---- replica select and scatter: Deleted and actors follow their documents ----
+ * crdt_awset_select_async / crdt_awset_scatter_async over a whole crdt_replica:
+ * the documents move with their AWSetDelta.Deleted tombstones and their actors,
+ * so a sparse delta round (digest, digest_diff, select both replicas, delta
+ * exchange, scatter both) and a sparse apply (select, apply, scatter) run with
+ * nothing downloaded, and select-all packs a replica whose tombstones carry the
+ * slack apply leaves.
+ * Document mapping: select's and scatter's.  Select: out gets n_out documents;
+ * for j < *n_idx document j is `rep` document idx[j] (idx == NULL: j), beyond it
+ * is empty.  Scatter: out gets rep->state->n_docs documents; document d is `sub`
+ * document j when idx[j] == d for some j < *n_idx (the lowest such j), and `rep`
+ * document d otherwise.  rep and sub must agree in R; their document counts and
+ * slot layouts are independent.
+ * State part: out->state is bit for bit what crdt_awset_select_async /
+ * crdt_awset_scatter_async write for the same state, idx, n_idx, n_out and
+ * out_slots = entry_slots: live entries, counts and VV, packed with no slack,
+ * offsets the exclusive prefix of the live counts, offsets[n_out] the total.
+ * idx == NULL, n_idx == NULL and n_out == n_docs is the compaction of the replica.
+ * Tombstones: the same document mapping over rep->tombs (or sub->tombs).  The
+ * live prefix (counts[d] slots, all slots when counts == NULL) is copied verbatim
+ * in its order, packed with no slack; out->tombs->offsets[n_out] is the total and
+ * counts are written.  A replica with tombs == NULL contributes empty ranges.  If
+ * no input replica has tombs, out->tombs may be NULL, and an out->tombs->offsets
+ * (and counts) that is passed is zeroed (the convention of sources).  Compaction
+ * of an apply output's tombstones (which sit at tombs.offsets[d] + op_off[d]) is
+ * this call with idx == NULL.
+ * Actors: when out->doc_actor != NULL, doc_actor[j] is the chosen source
+ * document's actor: doc_actor[d] of that replica, or its uniform `actor` when its
+ * doc_actor == NULL; empty documents beyond *n_idx get 0.
+ * out->state must hold n_out + 1 offsets, n_out counts, n_out * R clock words and
+ * entry_slots entries; out->tombs n_out + 1 offsets, n_out counts and tomb_slots
+ * tombstones; out->doc_actor n_out words.  Reported by crdt_ctx_sync:
+ *   select:  *n_idx > n_out  clamped to n_out, CRDT_E_CAPACITY
+ *            idx[j] >= n_docs  CRDT_E_INVALID; that document comes out empty
+ *   scatter: *n_idx > sub n_docs  clamped, CRDT_E_CAPACITY
+ *            idx[j] >= n_docs  CRDT_E_INVALID; that sub document is ignored
+ *            two j name one document: CRDT_E_INVALID; the lowest j supplies it
+ *   a live count above its slots, entries or tombstones, on either source:
+ *                         clamped, CRDT_E_CAPACITY
+ *   an entry total above entry_slots, or a tombstone total above tomb_slots
+ *                         (independently): CRDT_E_CAPACITY; nothing is written at
+ *                         or past the exceeded array's slots; offsets and totals
+ *                         stay exact (running totals in 64 bits)
+ * Returned by the call (CRDT_E_INVALID): rep, a state, out or out->state NULL, or
+ * one of its arrays; for scatter sub or idx NULL, or R different between rep and
+ * sub; R out of range; a tomb batch without offsets; out->tombs (or one of its
+ * arrays) NULL although an input replica has tombs; an output array starting
+ * where an input array of the same kind starts.
+ * Empty calls: with n_docs == 0 or n_out == 0, offsets[0] = 0 is written for
+ * entries and tombstones and nothing that reads documents is launched.
+ * Workspace: the partial sums of the offset scan, two words per 1,024 output
+ * documents, and for scatter one inverse-map word per document (0xFFFFFFFF = not
+ * replaced), in the context's buffers that crdt_ctx_reserve(max_docs, ..) sizes:
+ * no allocation on a reserved context, CRDT_E_WORKSPACE when they would have to
+ * grow during a graph capture.  The replica descriptors travel in the kernel
+ * arguments.  No host sync, kernel nodes only, capturable; ordered after the
+ * context's previous call like every entry point.  There is no _batch form. */
+typedef struct {                    /* one resident replica, written */
+    const crdt_awset_out* state;    /* required */
+    const crdt_tomb_out*  tombs;    /* required iff some input replica of the call has tombs; else may be NULL */
+    uint32_t* doc_actor;            /* [n_out documents], or NULL: actors not written */
+} crdt_replica_out;
+int crdt_replica_select_async(crdt_ctx* ctx, const crdt_replica* rep, const uint32_t* idx,
+                              const uint32_t* n_idx /* device, [1], or NULL */, uint32_t n_out,
+                              uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out, void* stream);
+int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub,
+                               const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */,
+                               uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out, void* stream);
 
 /* ---- delta merge of a resident replica pair ---------------------------------
  * (*AWSetDelta).Merge (awset-delta_test.go:51-65) applied to replicas in their
