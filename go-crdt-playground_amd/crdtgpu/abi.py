@@ -124,6 +124,15 @@ class CDiffOut(ctypes.Structure):
     ]
 
 
+class CMergeLog(ctypes.Structure):
+    _fields_ = [
+        ("flags", _vp), ("summary", _vp),
+        ("rem_offsets", _vp), ("rem_counts", _vp), ("rem_keys", _vp), ("rem_actors", _vp), ("rem_counters", _vp),
+        ("ups_offsets", _vp), ("ups_counts", _vp), ("ups_keys", _vp), ("ups_actors", _vp), ("ups_counters", _vp),
+        ("ups_kind", _vp),
+    ]
+
+
 class CReplica(ctypes.Structure):
     _fields_ = [("state", _vp), ("tombs", _vp), ("doc_actor", _vp), ("actor", _u32)]
 
@@ -210,6 +219,9 @@ def signatures():
         "crdt_awset_compare_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, P(CCompareOut)]),
         "crdt_awset_diff_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, _u32, P(CDiffOut), _vp]),
         "crdt_awset_diff_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _u32, _u32, P(CDiffOut)]),
+        "crdt_awset_join_log_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), P(CAWSetOut), P(CMergeLog), _vp]),
+        "crdt_awset_exchange_log_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), P(CAWSetOut), P(CAWSetOut),
+                                                         P(CMergeLog), P(CMergeLog), _vp]),
         "crdt_awset_digest_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp]),
         "crdt_awset_digest_host": (ctypes.c_int, [P(CAWSetBatch), P(CTombBatch), _vp]),
         "crdt_digest_diff_async": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, P(CCompareOut), _vp]),

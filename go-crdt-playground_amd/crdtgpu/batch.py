@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaOut, CSrcBatch,
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, CMergeLog, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaOut, CSrcBatch,
                   CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -589,6 +589,66 @@ class DiffBuffers:
                 out["%s_%s" % (side, col)] = None if a is None else _np(a, dt)[:m]
             if side == "ups":
                 out["ups_kind"] = None if self.ups_kind is None else _np(self.ups_kind, np.uint8)[:m]
+        return out
+
+
+class MergeLogBuffers:
+    """The log a logged join writes beside the merged state (crdt_merge_log): flags (u8
+    per doc, OR of CRDT_DIFF_*), summary (5 counts), and the two lists in the inputs' own
+    slot layouts -- removed in dst's (rem_offsets = dst.offsets, rem_counts, rem_keys,
+    rem_actors, rem_counters; rem_slots = dst's slots) and upserted in src's (ups_offsets,
+    ups_counts, ups_keys, ups_actors, ups_counters, ups_kind; ups_slots = src's slots).
+    kind / summary False: not asked for.  numpy, or torch on `device`."""
+
+    def __init__(self, n_docs, rem_slots, ups_slots, device=None, kind=True, summary=True):
+        self.n_docs = n = int(n_docs)
+        self.rem_slots, self.ups_slots = nr, nu = int(rem_slots), int(ups_slots)
+        if device is None:
+            z = lambda k, dt: np.zeros(max(k, 1), dt)  # noqa: E731
+            u8, u32, u64 = np.uint8, U32, U64
+        else:
+            import torch
+
+            z = lambda k, dt: torch.empty(max(k, 1), dtype=dt, device=device)  # noqa: E731
+            u8, u32, u64 = torch.uint8, torch.int32, torch.int64
+        self.flags = z(n, u8)
+        self.summary = z(5, u32) if summary else None
+        self.rem_offsets, self.ups_offsets = z(n + 1, u32), z(n + 1, u32)
+        self.rem_counts, self.ups_counts = z(n, u32), z(n, u32)
+        self.rem_keys, self.rem_actors, self.rem_counters = z(nr, u64), z(nr, u32), z(nr, u64)
+        self.ups_keys, self.ups_actors, self.ups_counters = z(nu, u64), z(nu, u32), z(nu, u64)
+        self.ups_kind = z(nu, u8) if kind else None
+
+    FIELDS = ("flags", "summary", "rem_offsets", "rem_counts", "rem_keys", "rem_actors", "rem_counters",
+              "ups_offsets", "ups_counts", "ups_keys", "ups_actors", "ups_counters", "ups_kind")
+    _DTYPES = (np.uint8, U32, U32, U32, U64, U32, U64, U32, U32, U64, U32, U64, np.uint8)
+
+    def c(self) -> CMergeLog:
+        return CMergeLog(*(ptr(getattr(self, f)) for f in self.FIELDS))
+
+    def removed(self) -> "TombBatch":
+        """The removed list as a TombBatch as it stands (offsets, counts and the three columns)."""
+        return TombBatch(self.rem_offsets[: self.n_docs + 1], self.rem_keys, self.rem_actors, self.rem_counters,
+                         counts=self.rem_counts[: self.n_docs])
+
+    def upserted(self) -> "TombBatch":
+        """The upserted list as a TombBatch as it stands."""
+        return TombBatch(self.ups_offsets[: self.n_docs + 1], self.ups_keys, self.ups_actors, self.ups_counters,
+                         counts=self.ups_counts[: self.n_docs])
+
+    def numpy(self):
+        """A dict of numpy arrays, one per field (absent: None): flags [n_docs], summary [5],
+        the offsets [n_docs + 1], the counts [n_docs] and the columns at their full slots."""
+        n = self.n_docs
+        size = {"flags": n, "summary": 5, "rem_offsets": n + 1, "ups_offsets": n + 1, "rem_counts": n, "ups_counts": n}
+        out = {}
+        for f, dt in zip(self.FIELDS, self._DTYPES):
+            a = getattr(self, f)
+            if a is None:
+                out[f] = None
+                continue
+            m = size.get(f, self.rem_slots if f.startswith("rem") else self.ups_slots)
+            out[f] = _np(a, dt)[:m]
         return out
 
 

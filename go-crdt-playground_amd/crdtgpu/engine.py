@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, ReplicaBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, ReplicaBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -172,6 +172,45 @@ class Engine:
         check(self._lib.crdt_awset_diff_async(self._ctx, ctypes.byref(cb), ctypes.byref(ca), int(rem_slots),
                                               int(ups_slots), ctypes.byref(co), _stream(stream)),
               "crdt_awset_diff_async")
+
+    def join_log_async(self, dst: AWSetBatch, src: AWSetBatch, out: OutBuffers, log: MergeLogBuffers, stream=None):
+        """join_async with the merge's log written beside the merged state: per doc, the dst
+        entries removed (in dst's slot layout) and the src entries added or moved to (in src's),
+        with CRDT_DIFF_* flags and the summary -- what diff_async(dst, out) reports, from the
+        one read the merge needs (crdt_awset_join_log_async)."""
+        d, s, o, lg = _c(dst), _c(src), _c(out), _c(log)
+        check(self._lib.crdt_awset_join_log_async(self._ctx, ctypes.byref(d), ctypes.byref(s), ctypes.byref(o),
+                                                  ctypes.byref(lg), _stream(stream)), "crdt_awset_join_log_async")
+
+    def exchange_log_async(self, a: AWSetBatch, b: AWSetBatch, out_ab: OutBuffers, out_ba: OutBuffers,
+                           log_ab: MergeLogBuffers, log_ba: MergeLogBuffers, stream=None):
+        """exchange_async with both directions' logs, from one read of both states: log_ab
+        removed in a's layout and upserted in b's, log_ba the other way round.  The two outputs
+        share no array, the key column included (crdt_awset_exchange_log_async)."""
+        ca, cb, o1, o2, l1, l2 = _c(a), _c(b), _c(out_ab), _c(out_ba), _c(log_ab), _c(log_ba)
+        check(self._lib.crdt_awset_exchange_log_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb), ctypes.byref(o1),
+                                                      ctypes.byref(o2), ctypes.byref(l1), ctypes.byref(l2),
+                                                      _stream(stream)), "crdt_awset_exchange_log_async")
+
+    def join_log(self, dst: AWSetBatch, src: AWSetBatch):
+        """Host batches uploaded, merged with the log on the device and downloaded: (the
+        merged state as host OutBuffers, MergeLogBuffers.numpy() of the log) (for tests and
+        small callers)."""
+        import numpy as np
+        import torch
+
+        dst, src = dst.numpy(), src.numpy()
+        n, R = dst.n_docs, dst.R
+        ds, ss = int(dst.offsets[-1]), int(src.offsets[-1])
+        dev = torch.device("cuda", self.device)
+        out = OutBuffers(n, R, ds + ss, device=dev)
+        log = MergeLogBuffers(n, ds, ss, device=dev)
+        self.join_log_async(dst.to(dev), src.to(dev), out, log)
+        self.sync()
+        h = OutBuffers(n, R, ds + ss)
+        h.offsets, h.counts, h.vv = _np(out.offsets, np.uint32), _np(out.counts, np.uint32), _np(out.vv, np.uint64)
+        h.keys, h.actors, h.counters = _np(out.keys, np.uint64), _np(out.actors, np.uint32), _np(out.counters, np.uint64)
+        return h, log.numpy()
 
     def digest_async(self, state: AWSetBatch, out, tombs: TombBatch = None, stream=None):
         """Per doc, the 16-byte digest of its live state into `out` (device u64 [2 * n_docs]):

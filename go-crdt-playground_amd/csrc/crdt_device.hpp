@@ -238,6 +238,24 @@ struct DiffOutView {
     uint8_t* ups_kind;  // NULL: none
 };
 
+// Logged join (join_log.hip): what crdt_awset_join_log_async writes beside the
+// merged state (same fields as crdt_merge_log).
+struct MergeLogView {
+    uint8_t* flags;
+    uint32_t* summary;  // NULL: none
+    uint32_t* rem_offsets;
+    uint32_t* rem_counts;
+    uint64_t* rem_keys;
+    uint32_t* rem_actors;
+    uint64_t* rem_counters;
+    uint32_t* ups_offsets;
+    uint32_t* ups_counts;
+    uint64_t* ups_keys;
+    uint32_t* ups_actors;
+    uint64_t* ups_counters;
+    uint8_t* ups_kind;  // NULL: none
+};
+
 // Workspace of the large-document tile path (tile.hip).  A call's tiles are
 // numbered 0 .. total-1 over all its documents and run in passes of at most
 // `cap` tiles (pass p: tiles [p*cap, p*cap + cap)); the per-tile arrays hold

@@ -769,6 +769,49 @@ func (e *Engine) ReplicaScatter(rep, sub *Replica, idx, nIdx *C.uint32_t, entryS
 	return nil
 }
 
+// ---------------------------------------------------------------- logged join
+
+// MergeLog is the device storage a logged join writes beside the merged state
+// (crdt_merge_log): per document the dst entries the merge removed, in dst's slot
+// layout, and the src entries it added or moved a common key to, in src's, with
+// the CRDT_DIFF_* flags and the summary. Every pointer is a device pointer;
+// summary and ups_kind may be nil.
+type MergeLog struct {
+	Log C.crdt_merge_log
+}
+
+// JoinLog is crdt_awset_join_async with the merge's decision log
+// (awset.go:109-158) written beside the merged state from the same read
+// (crdt_awset_join_log_async): out holds what the join writes; log's removed list
+// of document d starts at dst.offsets[d], its upserted list at src.offsets[d].
+// dst, src, out and log name device arrays. Asynchronous on stream; device-side
+// errors surface at the context's next sync.
+func (e *Engine) JoinLog(dst, src *C.crdt_awset_batch, out *C.crdt_awset_out, log *MergeLog,
+	stream unsafe.Pointer) error {
+	if dst == nil || src == nil || out == nil || log == nil {
+		return fmt.Errorf("JoinLog: nil argument")
+	}
+	if rc := C.crdt_awset_join_log_async(e.ctx, dst, src, out, &log.Log, stream); rc != 0 {
+		return errOf("crdt_awset_join_log_async", rc)
+	}
+	return nil
+}
+
+// ExchangeLog is crdt_awset_exchange_async with both directions' logs, from one
+// read of both states (crdt_awset_exchange_log_async): logAB's removed list is in
+// a's layout and its upserted list in b's, logBA's the other way round. The two
+// outputs share no array, the key column included.
+func (e *Engine) ExchangeLog(a, b *C.crdt_awset_batch, outAB, outBA *C.crdt_awset_out, logAB, logBA *MergeLog,
+	stream unsafe.Pointer) error {
+	if a == nil || b == nil || outAB == nil || outBA == nil || logAB == nil || logBA == nil {
+		return fmt.Errorf("ExchangeLog: nil argument")
+	}
+	if rc := C.crdt_awset_exchange_log_async(e.ctx, a, b, outAB, outBA, &logAB.Log, &logBA.Log, stream); rc != 0 {
+		return errOf("crdt_awset_exchange_log_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- state digests
 
 // HostBatch is a packed batch in host memory: State as arena.batch lays it out

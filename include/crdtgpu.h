@@ -48,6 +48,9 @@
  *       replace merge's decision log (update / add / remove per key,
  *       awset.go:109-158) in structured form: per document, the entries a
  *       merge removed and the entries it added or moved to another dot
+ *   crdt_awset_join_log_async / crdt_awset_exchange_log_async
+ *       the join and the exchange with that log written beside the merged
+ *       state, from the one read the merge needs   awset.go:103-161
  *   crdt_awset_sources_async
  *       P resident replicas of every document gathered into the packed source
  *       batch the folds and the delta extraction read (no reference
@@ -728,6 +731,73 @@ int crdt_awset_diff_async(crdt_ctx* ctx, const crdt_awset_batch* before, const c
                           uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out, void* stream);
 int crdt_awset_diff_batch(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
                           uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out);
+
+/* ---- logged join and exchange: the merge with its decision log ----------------
+ * crdt_awset_diff_* answers "what did the merge change" after the fact, from a
+ * second read of both batches and a search per key.  The joins' kernels have
+ * made every one of those decisions when they write the merged state (merge's
+ * log, awset.go:109-158): a dst-only key the src clock covers is a `remove`, a
+ * src-only key that survives an `add`, a common key whose dot changes an
+ * `update`.  These two calls write that log beside the merged state, from the
+ * one read the merge needs anyway.
+ * The merged state: out (out_ab, out_ba) holds what crdt_awset_join_async
+ * (crdt_awset_exchange_async) writes for the same inputs -- live entries,
+ * counts, offsets and clocks bit for bit, document d at dst.offsets[d] +
+ * src.offsets[d], slack unspecified.
+ * The log of direction dst <- src is crdt_awset_diff_*'s answer for before =
+ * dst, after = out, in a different layout.  Per document d:
+ *   - removed: the live entries of dst[d] whose key is not live in out[d], in
+ *     key order, with the dot they had in dst.
+ *   - upserted: the live entries of out[d] whose key was not live in dst[d]
+ *     (ups_kind CRDT_DIFF_ADDED) or was live there under a different (actor,
+ *     counter) (CRDT_DIFF_UPDATED), in key order, with their new dot.
+ *   - flags[d] and summary as crdt_awset_diff_async(dst, out) writes them,
+ *     CRDT_DIFF_CLOCK included.
+ * Layout: like every merge output, it needs no scan over documents.  A removed
+ * entry was a dst entry, so document d's removed list starts at dst.offsets[d]
+ * and holds rem_counts[d] entries, and rem_offsets repeats dst's slot bounds
+ * (n_docs + 1 values); an upserted entry was a src entry, so its list starts at
+ * src.offsets[d], holds ups_counts[d] entries, and ups_offsets repeats src's
+ * bounds.  Each list read as (offsets, counts, keys, actors, counters) is a
+ * valid crdt_tomb_batch as it stands.  Slots of a document at or past its count
+ * are unspecified; slots of other documents are never written.  The bits are the
+ * same on every run: no atomic decides a position (summary is a sum of integers).
+ * Exchange: both directions from one read, as crdt_awset_exchange_async defines
+ * them.  log_ab.removed is in a's layout and log_ab.upserted in b's; log_ba.removed
+ * is in b's layout and log_ba.upserted in a's.  The shared key column stays the
+ * plain exchange's: out_ba->keys == out_ab->keys is refused here.
+ * Only live prefixes are read (counts, or all slots when counts == NULL); the two
+ * batches' slot layouts are independent.
+ * Reported by crdt_ctx_sync:
+ *   CRDT_E_ACTOR_RANGE  any HasDot the merge evaluates at actor == R, as in the joins
+ *   CRDT_E_CAPACITY     a live count above its slots (clamped)
+ * Returned by the call (CRDT_E_INVALID): a NULL argument or a NULL required field
+ * (summary and ups_kind may be NULL); an n_docs or R mismatch; R out of range; two
+ * written arrays starting at one address (the shared key column included) or
+ * overlapping per-document arrays; a written array starting where an input array
+ * of the same kind starts.
+ * n_docs == 0 launches nothing that reads documents; summary, when given, is
+ * zeroed.  Ordered after the context's previous call; no host sync, kernel nodes
+ * only, capturable.  Workspace: the join's worklist, one word per
+ * document, sized by crdt_ctx_reserve(max_docs, ..); CRDT_E_WORKSPACE when it
+ * would have to grow during a graph capture; and a fixed 64 KB of summary partial
+ * sums in a buffer the context owns from its creation.  There is no _batch form. */
+typedef struct {            /* written */
+    uint8_t*  flags;        /* [n_docs] OR of CRDT_DIFF_REMOVED|ADDED|UPDATED|CLOCK */
+    uint32_t* summary;      /* [5] as crdt_diff_out.summary, may be NULL */
+    uint32_t* rem_offsets;  /* [n_docs+1] = dst.offsets */
+    uint32_t* rem_counts;   /* [n_docs] */
+    uint64_t* rem_keys;  uint32_t* rem_actors;  uint64_t* rem_counters;   /* capacity: dst's slots */
+    uint32_t* ups_offsets;  /* [n_docs+1] = src.offsets */
+    uint32_t* ups_counts;   /* [n_docs] */
+    uint64_t* ups_keys;  uint32_t* ups_actors;  uint64_t* ups_counters;   /* capacity: src's slots */
+    uint8_t*  ups_kind;     /* [src slots] CRDT_DIFF_ADDED | CRDT_DIFF_UPDATED, may be NULL */
+} crdt_merge_log;
+int crdt_awset_join_log_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_awset_batch* src,
+                              const crdt_awset_out* out, const crdt_merge_log* log, void* stream);
+int crdt_awset_exchange_log_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b,
+                                  const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
+                                  const crdt_merge_log* log_ab, const crdt_merge_log* log_ba, void* stream);
 
 /* ---- sources: resident replicas assembled into a fold / extraction input ----
  * Replicas live on the device as state batches (crdt_awset_batch, plus
