@@ -68,22 +68,12 @@ __device__ __forceinline__ uint32_t cmp_count_le(const uint32_t* a, uint32_t n, 
     return lo;
 }
 
-// Slot offset and live count of document d, the count clamped to the slots.
-__device__ __forceinline__ void cmp_live(const BatchView& v, uint32_t d, uint32_t& o, uint32_t& n, uint32_t& err) {
-    const uint32_t b = v.offsets[d], e = v.offsets[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = v.counts ? v.counts[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    n = min(live, slots);
-}
-
 // Document d of both sides: offsets, and the live count they share (0 when they differ).
 __device__ __forceinline__ void cmp_doc(const BatchView& a, const BatchView& b, uint32_t d, uint32_t& ao, uint32_t& bo,
                                         uint32_t& n) {
     uint32_t na, nb, err = 0;
-    cmp_live(a, d, ao, na, err);
-    cmp_live(b, d, bo, nb, err);
+    na = live_span(a.offsets, a.counts, d, ao, err);
+    nb = live_span(b.offsets, b.counts, d, bo, err);
     n = na == nb ? na : 0u;
 }
 
@@ -111,8 +101,8 @@ __global__ __launch_bounds__(256) void compare_docs_kernel(BatchView a, BatchVie
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_docs; i += (uint64_t)gridDim.x * 256) {
         const uint32_t d = (uint32_t)i;
         uint32_t ao, bo, na, nb;
-        cmp_live(a, d, ao, na, err);
-        cmp_live(b, d, bo, nb, err);
+        na = live_span(a.offsets, a.counts, d, ao, err);
+        nb = live_span(b.offsets, b.counts, d, bo, err);
         fw[d] = na != nb ? CRDT_CMP_KEYS : 0u;
     }
     flag_error(status, err);
@@ -407,7 +397,7 @@ __global__ __launch_bounds__(kScanNT) void select_scan_kernel(SelectArgs s, uint
                 const uint32_t d = sel_src(s, base + i, n_idx, err);
                 if (d != kNoDoc) {
                     uint32_t o;
-                    cmp_live(s.st, d, o, c, err);
+                    c = live_span(s.st.offsets, s.st.counts, d, o, err);
                 }
                 s.out.counts[base + i] = c;
                 mine += c;

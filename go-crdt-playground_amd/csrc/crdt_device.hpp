@@ -305,8 +305,24 @@ __device__ __forceinline__ uint32_t slab_chunk(const SlabMap& m, uint32_t c) {
     return ch < m.C ? ch : 0xFFFFFFFFu;
 }
 
+// The count as the producer wrote it, unclamped: for the callers that compare it
+// with the slots themselves (fold_block_kernel), only size work by it (the tile
+// geometry), or take it as given (join_block_kernel, apply.hip).
 __device__ __forceinline__ uint32_t live_count(const uint32_t* offsets, const uint32_t* counts, uint32_t d) {
     return counts ? counts[d] : offsets[d + 1] - offsets[d];
+}
+
+// Live prefix of document d of a five-array list: its first slot in o, its
+// length returned, clamped to the document's slots (kErrCapacity).  Offsets that
+// are not monotone (include/crdtgpu.h rules them out) give no slots: nothing is read.
+__device__ __forceinline__ uint32_t live_span(const uint32_t* off, const uint32_t* cnt, uint32_t d, uint32_t& o,
+                                              uint32_t& err) {
+    const uint32_t b = off[d], e = off[d + 1];
+    const uint32_t slots = e > b ? e - b : 0u;
+    const uint32_t live = cnt ? cnt[d] : slots;
+    if (live > slots) err |= kErrCapacity;
+    o = b;
+    return min(live, slots);
 }
 
 // VersionVector.HasDot (crdt-misc.go:28-34) against a VV of length R held in

@@ -23,11 +23,15 @@
 //    tombstones); then every lane decides its two keys and the survivors are
 //    compacted by ballot and popcount, as in join_wave_kernel, so the output is
 //    sorted by key and written once.  Larger documents go to the worklist.
-//  * delta_pair_block_kernel: workgroups pop the worklist; per direction one
-//    pass over src's entries and tombstones takes the kind, then block_merge
-//    runs in full or delta mode, or dst is copied for NONE.
+//    Staging, lookup, survivor placement, clock and slot bounds are shared with
+//    the logged join (merge_wave.hpp); the kind and the tombstones are here.
+//  * delta_pair_block_kernel: workgroups pop the worklist (for_each_work,
+//    merge_block.hpp); per direction one pass over src's entries and
+//    tombstones takes the kind (delta_changes), then block_merge runs in full
+//    or delta mode, or dst is copied for NONE.
 #include "crdt_device.hpp"
 #include "merge_block.hpp"
+#include "merge_wave.hpp"
 
 namespace crdt {
 
@@ -36,26 +40,10 @@ constexpr int kPairWaveMax = 64;   // live entries, and live tombstones, per sid
 constexpr int kPairBlockNT = 256;  // block path: threads per workgroup
 constexpr int kPairBlockIPT = 4;   // block path: merged positions per thread and window
 
-// Live prefix of document d of a five-array list: its first slot in o0, its
-// length returned, clamped to the document's slots (kErrCapacity).
-__device__ __forceinline__ uint32_t pair_live(const uint32_t* offsets, const uint32_t* counts, uint32_t d,
-                                              uint32_t& o0, uint32_t& err) {
-    o0 = offsets[d];
-    const uint32_t slots = offsets[d + 1] - o0;
-    uint32_t n = counts ? counts[d] : slots;
-    if (n > slots) {
-        n = slots;
-        err |= kErrCapacity;
-    }
-    return n;
-}
-
-// Per wave: index 0 = replica a, 1 = replica b.
-struct PairWaveSmem {
-    uint64_t ek[2][64], ec[2][64];  // entries
-    uint64_t tk[2][64], tc[2][64];  // tombstones
-    uint64_t vv[2][64];
-    uint32_t ea[2][64], ta[2][64];
+// Per wave: the entries and clocks (merge_wave.hpp) and both sides' tombstones.
+struct PairWaveSmem : WaveSmem {
+    uint64_t tk[2][64], tc[2][64];
+    uint32_t ta[2][64];
 };
 
 // One direction of a wave-path document: dst = side x of sm, src = side 1 - x.
@@ -64,71 +52,42 @@ __device__ __forceinline__ void pair_wave_dir(const PairWaveSmem& sm, uint32_t x
                                               uint32_t obase, const OutView& out, uint8_t* kind_out, uint32_t lane,
                                               uint32_t& err) {
     const uint32_t y = 1u - x;
-    const uint64_t* const dk = sm.ek[x];
-    const uint64_t* const sk = sm.ek[y];
-    const uint64_t* const dvv = sm.vv[x];
-    const uint64_t* const svv = sm.vv[y];
+    const WaveDir p = wave_lookup(sm, x, nd, ns, lane);
     const Entries tomb{sm.tk[y], sm.ta[y], sm.tc[y], nts};
-    const bool dv = lane < nd, sv = lane < ns, tv = lane < nts;
-    const uint64_t Dk = dk[lane], Dc = sm.ec[x][lane], Sk = sk[lane], Sc = sm.ec[y][lane];
-    const uint32_t Da = sm.ea[x][lane], Sa = sm.ea[y][lane];
 
     // the kind, before any entry is decided (:53, :60)
-    const bool full = uniform((uint32_t)(vv_counter(dvv, R, s_actor, err) == 0ull)) != 0u;
+    const bool full = uniform((uint32_t)(vv_counter(p.dvv, R, s_actor, err) == 0ull)) != 0u;
     uint32_t kind = CRDT_DELTA_FULL;
     if (!full) {
-        const bool changed = sv && !has_dot(dvv, R, Sa, Sc, err);
+        const bool changed = p.sv && !has_dot(p.dvv, R, p.Sa, p.Sc, err);
         bool effective = false;  // a tombstone the re-add filter lets through (:93-102)
-        if (tv) {
+        if (lane < nts) {
             const uint64_t Tk = sm.tk[y][lane];
-            const uint32_t m = lower_bound_pow<6>(sk, ns, Tk);
-            const bool readded = m < ns && sk[m & 63] == Tk &&
+            const uint32_t m = lower_bound_pow<6>(p.sk, ns, Tk);
+            const bool readded = m < ns && p.sk[m & 63] == Tk &&
                                  (sm.ea[y][m & 63] != sm.ta[y][lane] || sm.ec[y][m & 63] > sm.tc[y][lane]);
             effective = !readded;
         }
         kind = (ballot(changed) | ballot(effective)) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
     }
 
-    // # src keys < Dk, # dst keys < Sk
-    const uint32_t j = lower_bound_pow<6>(sk, ns, Dk);
-    const uint32_t i = lower_bound_pow<6>(dk, nd, Sk);
-    const bool dmatch = dv && j < ns && sk[j & 63] == Dk;
-    const bool smatch = sv && i < nd && dk[i & 63] == Sk;
     bool dkeep = false, skeep = false;
-    uint32_t oda = Da, osa = Sa;
-    uint64_t odc = Dc, osc = Sc;
+    uint32_t oda = p.Da, osa = p.Sa;
+    uint64_t odc = p.Dc, osc = p.Sc;
     if (kind == CRDT_DELTA_NONE) {
-        dkeep = dv;
+        dkeep = p.dv;
     } else {
-        if (dv)
-            dkeep = decide(true, Da, Dc, dmatch, dmatch ? sm.ea[y][j & 63] : 0u, dmatch ? sm.ec[y][j & 63] : 0ull, full,
-                           dvv, svv, R, tomb, Dk, oda, odc, err);
-        if (sv && !smatch) skeep = decide(false, 0u, 0ull, true, Sa, Sc, full, dvv, svv, R, tomb, Sk, osa, osc, err);
+        if (p.dv)
+            dkeep = decide(true, p.Da, p.Dc, p.dmatch, p.ja, p.jc, full, p.dvv, p.svv, R, tomb, p.Dk, oda, odc, err);
+        if (p.sv && !p.smatch)
+            skeep = decide(false, 0u, 0ull, true, p.Sa, p.Sc, full, p.dvv, p.svv, R, tomb, p.Sk, osa, osc, err);
     }
-    // a survivor's slot: kept lanes of its own side below it + kept entries of
-    // the other side with a smaller key
-    const uint64_t dm = ballot(dkeep), smk = ballot(skeep);
-    const uint32_t dpos = below(dm) + popc(smk & low_mask(j));
-    const uint32_t spos = below(smk) + popc(dm & low_mask(i));
-    const uint32_t n_out = popc(dm) + popc(smk);  // <= nd + ns <= the document's output slots
-    if (dkeep) {
-        out.keys[obase + dpos] = Dk;
-        out.actors[obase + dpos] = oda;
-        out.counters[obase + dpos] = odc;
-    }
-    if (skeep) {
-        out.keys[obase + spos] = Sk;
-        out.actors[obase + spos] = osa;
-        out.counters[obase + spos] = osc;
-    }
+    const uint32_t n_out = wave_place(p, dkeep, oda, odc, skeep, osa, osc, out, obase);
     if (lane == 0) {
         out.counts[d] = n_out;
         if (kind_out) kind_out[d] = (uint8_t)kind;
     }
-    if (lane < R) {
-        const uint64_t a = dvv[lane], b = svv[lane];
-        out.vv[(size_t)d * R + lane] = (kind == CRDT_DELTA_NONE || a > b) ? a : b;  // (:165; NONE: untouched)
-    }
+    wave_clock(p, kind == CRDT_DELTA_NONE, out, d, R, lane);  // (:165; NONE: untouched)
 }
 
 // EXCH: also out_ba = b <- a.  Without it a's tombstones are never read (A.tb is empty).
@@ -146,21 +105,15 @@ __global__ __launch_bounds__(WAVES * 64) void delta_pair_wave_kernel(PairSide A,
     uint32_t err = 0;
 
     uint32_t ao, bo, ato = 0, bto = 0;
-    const uint32_t na = pair_live(A.st.offsets, A.st.counts, d, ao, err);
-    const uint32_t nb = pair_live(B.st.offsets, B.st.counts, d, bo, err);
-    const uint32_t nta = (EXCH && A.tb.offsets) ? pair_live(A.tb.offsets, A.tb.counts, d, ato, err) : 0u;
-    const uint32_t ntb = B.tb.offsets ? pair_live(B.tb.offsets, B.tb.counts, d, bto, err) : 0u;
+    const uint32_t na = live_span(A.st.offsets, A.st.counts, d, ao, err);
+    const uint32_t nb = live_span(B.st.offsets, B.st.counts, d, bo, err);
+    const uint32_t nta = (EXCH && A.tb.offsets) ? live_span(A.tb.offsets, A.tb.counts, d, ato, err) : 0u;
+    const uint32_t ntb = B.tb.offsets ? live_span(B.tb.offsets, B.tb.counts, d, bto, err) : 0u;
     const uint32_t obase = ao + bo;
 
-    // slot bounds: every document, whichever path merges it
     if (lane == 0) {
-        o_ab.offsets[d] = obase;
-        if (EXCH) o_ba.offsets[d] = obase;
-        if (d == n_docs - 1) {
-            const uint32_t end_off = A.st.offsets[n_docs] + B.st.offsets[n_docs];
-            o_ab.offsets[n_docs] = end_off;
-            if (EXCH) o_ba.offsets[n_docs] = end_off;
-        }
+        pair_bounds(o_ab.offsets, nullptr, nullptr, A.st.offsets, B.st.offsets, d, n_docs, ao, bo);
+        if (EXCH) pair_bounds(o_ba.offsets, nullptr, nullptr, B.st.offsets, A.st.offsets, d, n_docs, bo, ao);
     }
     if (na > kPairWaveMax || nb > kPairWaveMax || nta > kPairWaveMax || ntb > kPairWaveMax) {
         if (lane == 0) push_work(wk, d, n_docs);
@@ -168,31 +121,9 @@ __global__ __launch_bounds__(WAVES * 64) void delta_pair_wave_kernel(PairSide A,
         return;
     }
 
-    // both replicas' document, once
-    if (lane < na) {
-        sm.ek[0][lane] = A.st.keys[ao + lane];
-        sm.ea[0][lane] = A.st.actors[ao + lane];
-        sm.ec[0][lane] = A.st.counters[ao + lane];
-    }
-    if (lane < nb) {
-        sm.ek[1][lane] = B.st.keys[bo + lane];
-        sm.ea[1][lane] = B.st.actors[bo + lane];
-        sm.ec[1][lane] = B.st.counters[bo + lane];
-    }
-    if (lane < nta) {
-        sm.tk[0][lane] = A.tb.keys[ato + lane];
-        sm.ta[0][lane] = A.tb.actors[ato + lane];
-        sm.tc[0][lane] = A.tb.counters[ato + lane];
-    }
-    if (lane < ntb) {
-        sm.tk[1][lane] = B.tb.keys[bto + lane];
-        sm.ta[1][lane] = B.tb.actors[bto + lane];
-        sm.tc[1][lane] = B.tb.counters[bto + lane];
-    }
-    if (lane < R) {
-        sm.vv[0][lane] = A.st.vv[(size_t)d * R + lane];
-        sm.vv[1][lane] = B.st.vv[(size_t)d * R + lane];
-    }
+    wave_stage_pair(sm, A.st, B.st, d, ao, na, bo, nb, lane);
+    wave_stage(sm.tk[0], sm.ta[0], sm.tc[0], A.tb.keys, A.tb.actors, A.tb.counters, ato, nta, lane);
+    wave_stage(sm.tk[1], sm.ta[1], sm.tc[1], B.tb.keys, B.tb.actors, B.tb.counters, bto, ntb, lane);
     wave_sync();
 
     const uint32_t b_actor = B.doc_actor ? B.doc_actor[d] : B.actor;
@@ -206,13 +137,13 @@ __global__ __launch_bounds__(WAVES * 64) void delta_pair_wave_kernel(PairSide A,
 
 // One direction of a block-path document, by the whole workgroup.
 template <int NT, int IPT>
-__device__ void pair_block_dir(const PairSide& Dd, const PairSide& Sd, uint32_t d, uint32_t R,
+__device__ __forceinline__ void pair_block_dir(const PairSide& Dd, const PairSide& Sd, uint32_t d, uint32_t R,
                                MergeSmem<NT, IPT>& sm, const OutView& out, uint8_t* kind_out, uint32_t& err) {
     const uint32_t tid = threadIdx.x;
     uint32_t doff, soff, toff = 0;
-    const uint32_t nd = pair_live(Dd.st.offsets, Dd.st.counts, d, doff, err);
-    const uint32_t ns = pair_live(Sd.st.offsets, Sd.st.counts, d, soff, err);
-    const uint32_t nt = Sd.tb.offsets ? pair_live(Sd.tb.offsets, Sd.tb.counts, d, toff, err) : 0u;
+    const uint32_t nd = live_span(Dd.st.offsets, Dd.st.counts, d, doff, err);
+    const uint32_t ns = live_span(Sd.st.offsets, Sd.st.counts, d, soff, err);
+    const uint32_t nt = Sd.tb.offsets ? live_span(Sd.tb.offsets, Sd.tb.counts, d, toff, err) : 0u;
     const Entries D{Dd.st.keys + doff, Dd.st.actors + doff, Dd.st.counters + doff, nd};
     const Entries S{Sd.st.keys + soff, Sd.st.actors + soff, Sd.st.counters + soff, ns};
     const Entries T{nt ? Sd.tb.keys + toff : nullptr, nt ? Sd.tb.actors + toff : nullptr,
@@ -225,18 +156,8 @@ __device__ void pair_block_dir(const PairSide& Dd, const PairSide& Sd, uint32_t 
     const uint32_t s_actor = Sd.doc_actor ? Sd.doc_actor[d] : Sd.actor;
     const bool full = vv_counter(sm.dvv, R, s_actor, err) == 0ull;  // (every thread reads the same words)
     uint32_t kind = CRDT_DELTA_FULL;
-    if (!full) {
-        bool any = false;
-        for (uint32_t t = tid; t < ns; t += NT) any |= !has_dot(sm.dvv, R, S.a[t], S.c[t], err);  // changed, :84-92
-        for (uint32_t t = tid; t < nt; t += NT) {  // the re-add filter, :93-102
-            uint32_t ea;
-            uint64_t ec;
-            const bool readded = tomb_find(S, T.k[t], ea, ec) && (ea != T.a[t] || ec > T.c[t]);
-            any |= !readded;
-        }
-        kind = __syncthreads_or(any) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
-    }
-    const uint32_t obase = Dd.st.offsets[d] + Sd.st.offsets[d];
+    if (!full) kind = delta_changes<NT>(S, T, sm.dvv, R, err) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
+    const uint32_t obase = doff + soff;
     const EntriesOut O{out.keys + obase, out.actors + obase, out.counters + obase};
     uint32_t n;
     if (kind == CRDT_DELTA_NONE) {
@@ -264,25 +185,12 @@ template <int NT, int IPT, bool EXCH>
 __global__ __launch_bounds__(NT) void delta_pair_block_kernel(PairSide A, PairSide B, OutView o_ab, OutView o_ba,
                                                               uint8_t* kind_ab, uint8_t* kind_ba, Work wk) {
     __shared__ MergeSmem<NT, IPT> sm;
-    const uint32_t tid = threadIdx.x;
     const uint32_t R = A.st.R, n_docs = A.st.n_docs;
     uint32_t err = 0;
-    if (work_total(wk, n_docs) == 0) return;  // empty worklist (set by the previous launch)
-    for (;;) {
-        if (tid == 0) sm.word[0] = atomicAdd(wk.wl_head, 1u);
-        __syncthreads();
-        const uint32_t slot = sm.word[0];
-        const uint32_t total = work_total(wk, n_docs);
-        __syncthreads();
-        if (slot >= total) break;
-        const uint32_t d = wk.worklist[slot];
-        if (d >= n_docs) {  // not a document of this call: never dereferenced
-            if (tid == 0) atomicOr(wk.status, kErrWorkspace);
-            continue;
-        }
+    for_each_work(wk, 0u, n_docs, &sm.word[0], [&](uint32_t d) {
         pair_block_dir<NT, IPT>(A, B, d, R, sm, o_ab, kind_ab, err);
         if (EXCH) pair_block_dir<NT, IPT>(B, A, d, R, sm, o_ba, kind_ba, err);
-    }
+    });
     flag_error(wk.status, err);
 }
 

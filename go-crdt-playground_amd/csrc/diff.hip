@@ -104,16 +104,6 @@ __device__ __forceinline__ uint32_t diff_count_lt(const uint32_t* a, uint32_t n,
     return lo;
 }
 
-// Slot offset and live count of document d, the count clamped to the slots.
-__device__ __forceinline__ void diff_live(const BatchView& v, uint32_t d, uint32_t& o, uint32_t& n, uint32_t& err) {
-    const uint32_t b = v.offsets[d], e = v.offsets[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = v.counts ? v.counts[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    n = min(live, slots);
-}
-
 // How a side's slot space is cut up: chunks of kDiffChunk positions, dealt in
 // groups of `group` consecutive chunks to n_parts <= kDiffMaxParts workgroups.
 struct DiffGeo {
@@ -225,8 +215,8 @@ __device__ __forceinline__ uint32_t diff_chunk(const DiffArgs& a, uint32_t base,
     if (staged) {
         for (uint32_t i = t; i < span; i += kDiffNT) {
             uint32_t xo, xn, yo, yn;
-            diff_live(x, d_lo + i, xo, xn, err);
-            diff_live(y, d_lo + i, yo, yn, err);
+            xn = live_span(x.offsets, x.counts, d_lo + i, xo, err);
+            yn = live_span(y.offsets, y.counts, d_lo + i, yo, err);
             sm.xo[i] = xo;
             sm.xn[i] = xn;
             sm.yo[i] = yo;
@@ -258,8 +248,8 @@ __device__ __forceinline__ uint32_t diff_chunk(const DiffArgs& a, uint32_t base,
                 ny[j] = sm.yn[i];
             } else {
                 dd[j] = d_lo + diff_count_le(x.offsets + 1 + d_lo, span - 1, p);
-                diff_live(x, dd[j], xo, xn, err);
-                diff_live(y, dd[j], yb[j], ny[j], err);
+                xn = live_span(x.offsets, x.counts, dd[j], xo, err);
+                ny[j] = live_span(y.offsets, y.counts, dd[j], yb[j], err);
             }
             const uint32_t i = p - xo;  // (below the document: wraps, never < xn)
             live[j] = i < xn;
@@ -377,9 +367,9 @@ __global__ __launch_bounds__(256) void diff_init_kernel(BatchView before, BatchV
     uint32_t err = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < before.n_docs; i += (uint64_t)gridDim.x * 256) {
         const uint32_t d = (uint32_t)i;
-        uint32_t o, n;
-        diff_live(before, d, o, n, err);
-        diff_live(after, d, o, n, err);
+        uint32_t o;
+        live_span(before.offsets, before.counts, d, o, err);
+        live_span(after.offsets, after.counts, d, o, err);
         fw[d] = 0u;
     }
     flag_error(status, err);

@@ -62,16 +62,6 @@ __device__ __forceinline__ uint32_t dig_count_le(const uint32_t* a, uint32_t n, 
     return lo;
 }
 
-// Slot offset and live count of document d, the count clamped to the slots.
-__device__ __forceinline__ void dig_live(const HasView& v, uint32_t d, uint32_t& o, uint32_t& n, uint32_t& err) {
-    const uint32_t b = v.offsets[d], e = v.offsets[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = v.counts ? v.counts[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    n = min(live, slots);
-}
-
 // G = 1 << g_log lanes per document (G >= R, G <= 64): lane r of a group holds
 // clock word r.  tb.offsets == NULL: no tombstones.
 __global__ __launch_bounds__(256) void digest_init_kernel(HasView st, HasView tb, const uint64_t* vv, uint32_t R,
@@ -89,8 +79,8 @@ __global__ __launch_bounds__(256) void digest_init_kernel(HasView st, HasView tb
         for (uint32_t o = G >> 1; o > 0; o >>= 1) h += (uint64_t)__shfl_xor((ull)h, (int)o);
         if (doc && r == 0) {
             uint32_t o, n, m = 0;
-            dig_live(st, d, o, n, err);
-            if (tb.offsets) dig_live(tb, d, o, m, err);
+            n = live_span(st.offsets, st.counts, d, o, err);
+            if (tb.offsets) m = live_span(tb.offsets, tb.counts, d, o, err);
             digest[2 * (size_t)d] = kDigN * n;
             digest[2 * (size_t)d + 1] = h + kDigN * ((uint64_t)n + m);
         }
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(kDigNT) void digest_entries_kernel(HasView v, uint6
         if (staged) {
             for (uint32_t x = t; x < span; x += kDigNT) {
                 uint32_t o, n, err = 0;  // (reported by digest_init_kernel)
-                dig_live(v, d_lo + x, o, n, err);
+                n = live_span(v.offsets, v.counts, d_lo + x, o, err);
                 s_o[x] = o;
                 s_n[x] = n;
                 if (!TOMB) s_w0[x] = 0;
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(kDigNT) void digest_entries_kernel(HasView v, uint6
             } else {
                 uint32_t err = 0;
                 r.d = d_lo + dig_count_le(v.offsets + 1 + d_lo, span - 1, p);
-                dig_live(v, r.d, o, r.n, err);
+                r.n = live_span(v.offsets, v.counts, r.d, o, err);
             }
             r.i = p - o;  // (below the document: wraps, never < n)
             r.live = r.i < r.n;

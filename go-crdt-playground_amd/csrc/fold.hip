@@ -1583,19 +1583,7 @@ __global__ __launch_bounds__(NT) void fold_block_kernel(int mode, BatchView dst,
     const uint32_t tid = threadIdx.x;
     const uint32_t R = dst.R;
     uint32_t err = 0;
-    if (work_total(wk, dst.n_docs) == 0) return;  // empty worklist (set by the previous launch): no dispensing atomics
-    for (;;) {
-        if (tid == 0) sm.word[0] = atomicAdd(wk.wl_head, 1u);
-        __syncthreads();
-        const uint32_t slot = sm.word[0];
-        const uint32_t total = work_total(wk, dst.n_docs);
-        __syncthreads();
-        if (slot >= total) break;
-        const uint32_t d = wk.worklist[slot];
-        if (d >= dst.n_docs) {  // not a document of this call: never dereferenced
-            if (tid == 0) atomicOr(wk.status, kErrWorkspace);
-            continue;
-        }
+    for_each_work(wk, 0u, dst.n_docs, &sm.word[0], [&](uint32_t d) {
         const uint32_t s0 = sb.doc_srcs[d], s1 = sb.doc_srcs[d + 1];
         const uint32_t doff = dst.offsets[d];
         const uint32_t dslots = dst.offsets[d + 1] - doff;
@@ -1604,7 +1592,7 @@ __global__ __launch_bounds__(NT) void fold_block_kernel(int mode, BatchView dst,
         if ((uint64_t)obase + cap > scr.slots) {  // crdt_ctx_reserve was not told enough slots
             if (tid == 0) atomicOr(wk.status, kErrWorkspace);
             __syncthreads();
-            continue;
+            return;
         }
         const EntriesOut O{out.keys + obase, out.actors + obase, out.counters + obase};
         const EntriesOut X{scr.keys + obase, scr.actors + obase, scr.counters + obase};
@@ -1632,16 +1620,7 @@ __global__ __launch_bounds__(NT) void fold_block_kernel(int mode, BatchView dst,
                 stop = true;
                 break;
             }
-            if (!full) {
-                bool any = false;
-                for (uint32_t e = tid; e < S.n; e += NT) any |= !has_dot(sm.dvv, R, S.a[e], S.c[e], err);
-                for (uint32_t t = tid; t < Tm.n; t += NT) {
-                    const uint32_t g = lower_bound(S.k, S.n, Tm.k[t]);
-                    const bool in_s = g < S.n && S.k[g] == Tm.k[t];
-                    any |= !(in_s && (S.a[g] != Tm.a[t] || S.c[g] > Tm.c[t]));
-                }
-                if (!__syncthreads_or(any)) continue;
-            }
+            if (!full && !delta_changes<NT>(S, Tm, sm.dvv, R, err)) continue;
             const EntriesOut& tgt = (where == 1) ? X : O;
             const uint32_t n = block_merge<NT, IPT>(cur, S, full ? Entries{nullptr, nullptr, nullptr, 0} : Tm, full, R,
                                                     sm, tgt, err);
@@ -1660,7 +1639,7 @@ __global__ __launch_bounds__(NT) void fold_block_kernel(int mode, BatchView dst,
         if (tid == 0) out.counts[d] = cur.n;
         if (tid < R) out.vv[(size_t)d * R + tid] = sm.dvv[tid];
         __syncthreads();
-    }
+    });
     if (__syncthreads_or(err != 0) && tid == 0) atomicOr(wk.status, kErrActorRange);
 }
 

@@ -399,19 +399,7 @@ __global__ __launch_bounds__(NT) void join_block_kernel(BatchView dst, BatchView
     const uint32_t R = dst.R;
     uint32_t err = 0;
     const Entries none{nullptr, nullptr, nullptr, 0};
-    if (work_total(wk, dst.n_docs) == 0) return;  // empty worklist (set by the previous launch): no dispensing atomics
-    for (;;) {
-        if (tid == 0) sm.word[0] = atomicAdd(wk.wl_head + head, 1u);
-        __syncthreads();
-        const uint32_t slot = sm.word[0];
-        const uint32_t total = work_total(wk, dst.n_docs);
-        __syncthreads();
-        if (slot >= total) break;
-        const uint32_t d = wk.worklist[slot];
-        if (d >= dst.n_docs) {  // not a document of this call: never dereferenced
-            if (tid == 0) atomicOr(wk.status, kErrWorkspace);
-            continue;
-        }
+    for_each_work(wk, head, dst.n_docs, &sm.word[0], [&](uint32_t d) {
         const uint32_t doff = dst.offsets[d], soff = src.offsets[d];
         const Entries D{dst.keys + doff, dst.actors + doff, dst.counters + doff, live_count(dst.offsets, dst.counts, d)};
         const Entries S{src.keys + soff, src.actors + soff, src.counters + soff, live_count(src.offsets, src.counts, d)};
@@ -426,7 +414,7 @@ __global__ __launch_bounds__(NT) void join_block_kernel(BatchView dst, BatchView
         if (tid == 0) out.counts[d] = n;
         if (tid < R) out.vv[(size_t)d * R + tid] = max(sm.dvv[tid], sm.svv[tid]);
         __syncthreads();
-    }
+    });
     if (__syncthreads_or(err != 0) && tid == 0) atomicOr(wk.status, kErrActorRange);
 }
 

@@ -6,6 +6,13 @@
 // with the per-key rule (DESIGN.md "Per-key rule"), and the workgroup scans the
 // kept counts to place the survivors contiguously in key order.
 //
+// The walk exists once (merge_walk).  What it writes is its sink's business:
+// block_merge places the survivors (KeepSink: join.hip, fold.hip, delta_pair.hip);
+// the logged join adds the removed and upserted records beside them (LogSink,
+// join_log.hip).  The file also holds what the four block kernels share around
+// the walk: the worklist loop (for_each_work) and the test whether a delta source
+// changes anything (delta_changes).
+//
 // The rule (union key k, dst dot d if present, src dot s if present):
 //   changed  = has_s && (full || !dstVV.HasDot(s))   awset-delta_test.go:84-92
 //   has_d && has_s : present, dot = changed ? s : d   awset.go:123-129,142
@@ -127,14 +134,61 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* w
     return base + x - v;
 }
 
-// Merge one document.  sm.dvv / sm.svv must hold the two version vectors.
-// Returns the number of entries written to out.
-template <int NT, int IPT>
-__device__ uint32_t block_merge(const Entries& D, const Entries& S, const Entries& tomb, bool full, uint32_t R,
-                                MergeSmem<NT, IPT>& sm, const EntriesOut& out, uint32_t& err) {
+// What decide() made of one merged position of the window walk.  A keep / drop
+// sink reads kPosKeep alone; the logged join's sink (join_log.hip) reads all four.
+constexpr uint8_t kPosKeep = 1;  // survives, with the merged dot
+constexpr uint8_t kPosRem = 2;   // a dst entry the merge dropped
+constexpr uint8_t kPosAdd = 4;   // a src-only key the merge kept
+constexpr uint8_t kPosUpd = 8;   // a common key whose dot the merge changed
+
+__device__ __forceinline__ void put_entry(const EntriesOut& e, uint32_t p, uint64_t k, uint32_t a, uint64_t c) {
+    e.k[p] = k;
+    e.a[p] = a;
+    e.c[p] = c;
+}
+
+// The keep / drop sink: the survivors, contiguous in key order.
+struct KeepSink {
+    static constexpr bool kLog = false;
+    EntriesOut out;
+    uint32_t o;  // survivors written so far
+
+    // One window: thread-local classes and records of IPT positions -> one block scan, the stores.
+    template <int NT, int IPT>
+    __device__ __forceinline__ void place(const uint8_t (&cls)[IPT], const uint64_t (&ok)[IPT],
+                                          const uint32_t (&oa)[IPT], const uint64_t (&oc)[IPT], uint32_t* wave_tot) {
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) cnt += (cls[q] & kPosKeep) ? 1u : 0u;
+        uint32_t total;
+        uint32_t pos = o + block_exclusive_scan<NT>(cnt, wave_tot, &total);
+#pragma unroll
+        for (int q = 0; q < IPT; ++q)
+            if (cls[q] & kPosKeep) put_entry(out, pos++, ok[q], oa[q], oc[q]);
+        o += total;
+    }
+};
+
+// The merge-path window walk of one document, dst <- src (+ tombstones), by the
+// whole workgroup.  sm.dvv / sm.svv must hold the two version vectors.  Each
+// window's positions are classified (kPos*) and handed to sink.place with the key
+// and the dot their record carries: the merged dot of a survivor, and of a dropped
+// dst entry its own, which decide returns too.
+//
+// A common key is classified where its dst entry is taken, which always sees the
+// src entry (the src window reaches a whole window ahead), so a pair that
+// straddles a window boundary is kept, UPDATED or dropped exactly once; the src
+// entry is skipped in the next window by prev_dk.
+//
+// (Not __forceinline__, like block_merge: inlined early, the walk costs the keep /
+// drop kernels 20 to 30 VGPRs; the callers that pop the worklist are forced
+// instead, so that no kernel ends up with a call.)
+template <int NT, int IPT, class Sink>
+__device__ void merge_walk(const Entries& D, const Entries& S, const Entries& tomb, bool full,
+                                           uint32_t R, MergeSmem<NT, IPT>& sm, Sink& sink, uint32_t& err) {
     constexpr uint32_t T = NT * IPT;
     const uint32_t tid = threadIdx.x;
-    uint32_t i = 0, j = 0, o = 0;
+    uint32_t i = 0, j = 0;
     while (i < D.n || j < S.n) {
         const uint32_t nd = min(T, D.n - i), ns = min(T, S.n - j);
         const uint32_t K = min(T, nd + ns);
@@ -159,11 +213,10 @@ __device__ uint32_t block_merge(const Entries& D, const Entries& S, const Entrie
         uint64_t ok[IPT];
         uint32_t oa[IPT];
         uint64_t oc[IPT];
-        bool kp[IPT];
-        uint32_t cnt = 0;
+        uint8_t cls[IPT];
 #pragma unroll
         for (int q = 0; q < IPT; ++q) {
-            kp[q] = false;
+            cls[q] = 0;
             ok[q] = 0;
             oa[q] = 0;
             oc[q] = 0;
@@ -171,44 +224,87 @@ __device__ uint32_t block_merge(const Entries& D, const Entries& S, const Entrie
                 const bool take_d = (a < nd) && (b >= ns || sm.dk[a] <= sm.sk[b]);
                 if (take_d) {
                     const uint64_t key = sm.dk[a];
+                    // (b < ns whenever src has an entry left: the src window reaches T entries ahead)
                     const bool match = (b < ns) && sm.sk[b] == key;
-                    uint32_t s_a = match ? sm.sa[b] : 0u;
-                    uint64_t s_c = match ? sm.sc[b] : 0ull;
-                    kp[q] = decide(true, sm.da[a], sm.dc[a], match, s_a, s_c, full, sm.dvv, sm.svv, R, tomb, key,
-                                   oa[q], oc[q], err);
+                    const uint32_t d_a = sm.da[a], s_a = match ? sm.sa[b] : 0u;
+                    const uint64_t d_c = sm.dc[a], s_c = match ? sm.sc[b] : 0ull;
+                    const bool kp = decide(true, d_a, d_c, match, s_a, s_c, full, sm.dvv, sm.svv, R, tomb, key, oa[q],
+                                           oc[q], err);
                     ok[q] = key;
+                    cls[q] = kp ? kPosKeep : kPosRem;
+                    if (Sink::kLog && match && (oa[q] != d_a || oc[q] != d_c)) cls[q] |= kPosUpd;
                     ++a;
                 } else {
                     const uint64_t key = sm.sk[b];
                     const bool match = (a > 0) ? (sm.dk[a - 1] == key) : (has_prev && prev_dk == key);
                     if (!match) {
-                        kp[q] = decide(false, 0u, 0ull, true, sm.sa[b], sm.sc[b], full, sm.dvv, sm.svv, R, tomb, key,
-                                       oa[q], oc[q], err);
+                        const bool kp = decide(false, 0u, 0ull, true, sm.sa[b], sm.sc[b], full, sm.dvv, sm.svv, R, tomb,
+                                               key, oa[q], oc[q], err);
                         ok[q] = key;
+                        cls[q] = kp ? (kPosKeep | kPosAdd) : 0;
                     }
                     ++b;
                 }
-                cnt += kp[q] ? 1u : 0u;
             }
         }
-        uint32_t total;
-        uint32_t pos = o + block_exclusive_scan<NT>(cnt, sm.wave_tot, &total);
-#pragma unroll
-        for (int q = 0; q < IPT; ++q) {
-            if (kp[q]) {
-                out.k[pos] = ok[q];
-                out.a[pos] = oa[q];
-                out.c[pos] = oc[q];
-                ++pos;
-            }
-        }
+        sink.template place<NT, IPT>(cls, ok, oa, oc, sm.wave_tot);
         const uint32_t aK = merge_path(sm.dk, nd, sm.sk, ns, K);
         i += aK;
         j += K - aK;
-        o += total;
         __syncthreads();
     }
-    return o;
+}
+
+// Merge one document, keep / drop.  Returns the number of entries written to out.
+template <int NT, int IPT>
+__device__ uint32_t block_merge(const Entries& D, const Entries& S, const Entries& tomb, bool full, uint32_t R,
+                                MergeSmem<NT, IPT>& sm, const EntriesOut& out, uint32_t& err) {
+    KeepSink sink{out, 0u};
+    merge_walk<NT, IPT>(D, S, tomb, full, R, sm, sink, err);
+    return sink.o;
+}
+
+// Does a delta source (entries S, tombstones T) change a dst whose clock is dvv:
+// some entry has a dot dst has not seen (changed, awset-delta_test.go:84-92) or
+// some tombstone passes the re-add filter (:93-102).  The whole workgroup calls it.
+template <int NT>
+__device__ __forceinline__ bool delta_changes(const Entries& S, const Entries& T, const uint64_t* dvv, uint32_t R,
+                                              uint32_t& err) {
+    const uint32_t tid = threadIdx.x;
+    bool any = false;
+    for (uint32_t e = tid; e < S.n; e += NT) any |= !has_dot(dvv, R, S.a[e], S.c[e], err);
+    for (uint32_t t = tid; t < T.n; t += NT) {
+        uint32_t ea;
+        uint64_t ec;
+        const bool readded = tomb_find(S, T.k[t], ea, ec) && (ea != T.a[t] || ec > T.c[t]);
+        any |= !readded;
+    }
+    return __syncthreads_or(any) != 0;
+}
+
+// The block path's worklist: workgroups pop documents from head word `head` of
+// wk.wl_head (the exchange of join.hip runs the list twice, once per direction)
+// until the list the previous launch filled is empty, and call body(d) for each.
+// `word` is one LDS word.  An entry that is not a document of this call is never
+// dereferenced (kErrWorkspace).
+template <class Body>
+__device__ __forceinline__ void for_each_work(const Work& wk, uint32_t head, uint32_t n_docs, uint32_t* word,
+                                              Body&& body) {
+    if (work_total(wk, n_docs) == 0) return;  // empty worklist: no dispensing atomics
+    for (;;) {
+        if (threadIdx.x == 0) *word = atomicAdd(wk.wl_head + head, 1u);
+        __syncthreads();
+        const uint32_t slot = *word;
+        const uint32_t total = work_total(wk, n_docs);
+        __syncthreads();
+        if (slot >= total) break;
+        const uint32_t d = wk.worklist[slot];
+        if (d >= n_docs) {
+            if (threadIdx.x == 0) atomicOr(wk.status, kErrWorkspace);
+            continue;
+        }
+        body(d);
+    }
 }
 
 }  // namespace crdt

@@ -73,18 +73,6 @@ __device__ __forceinline__ uint32_t rep_count_le(const uint32_t* a, uint32_t n, 
     return lo;
 }
 
-// Slot offset and live count of document d of one column set, the count clamped to the slots.
-__device__ __forceinline__ uint32_t rep_live(const SrcCols& c, uint32_t d, uint32_t& o, uint32_t& err) {
-    o = 0;
-    if (!c.off) return 0u;
-    const uint32_t b = c.off[d], e = c.off[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = c.cnt ? c.cnt[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    return min(live, slots);
-}
-
 // Documents a select takes (the rest of the n_out come out empty).
 __device__ __forceinline__ uint32_t rep_n_idx(const ReplicaArgs& s, uint32_t& err) {
     if (s.inv) return 0u;  // (scatter: read by replica_map_kernel alone)
@@ -161,8 +149,8 @@ __global__ __launch_bounds__(kRepNT) void replica_count_kernel(ReplicaArgs s, ui
             uint32_t side, d, o;
             if (rep_pick(s, base + i, n_idx, side, d, err)) {
                 const RepSide& r = side ? s.sub : s.rep;
-                me += rep_live(r.e, d, o, err);
-                mt += rep_live(r.t, d, o, err);
+                me += (r.e.off ? live_span(r.e.off, r.e.cnt, d, o, err) : 0u);
+                mt += (r.t.off ? live_span(r.t.off, r.t.cnt, d, o, err) : 0u);
             }
         }
     }
@@ -249,8 +237,8 @@ __global__ __launch_bounds__(kRepNT) void replica_emit_kernel(ReplicaArgs s, con
             uint32_t side, d, o, actor = 0;
             if (rep_pick(s, base + i, n_idx, side, d, err)) {
                 const RepSide& r = side ? s.sub : s.rep;
-                ce = rep_live(r.e, d, o, err);
-                ct = rep_live(r.t, d, o, err);
+                ce = r.e.off ? live_span(r.e.off, r.e.cnt, d, o, err) : 0u;
+                ct = r.t.off ? live_span(r.t.off, r.t.cnt, d, o, err) : 0u;
                 actor = r.doc_actor ? r.doc_actor[d] : r.actor;
             }
             s.out.counts[base + i] = ce;

@@ -73,26 +73,16 @@ __device__ __forceinline__ uint32_t sct_count_le(const uint32_t* a, uint32_t n, 
     return lo;
 }
 
-// Slot offset and live count of document d, the count clamped to the slots.
-__device__ __forceinline__ void sct_live(const BatchView& v, uint32_t d, uint32_t& o, uint32_t& n, uint32_t& err) {
-    const uint32_t b = v.offsets[d], e = v.offsets[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = v.counts ? v.counts[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    n = min(live, slots);
-}
-
 // The source of output document d: sub document j = inv[d], or the state's own
 // (j == kSctNone); its slot offset and clamped live count.
 __device__ __forceinline__ void sct_doc(const ScatterArgs& s, const uint32_t* inv, uint32_t d, uint32_t& j,
                                         uint32_t& o, uint32_t& n, uint32_t& err) {
     j = inv[d];
     if (j < s.sub.n_docs) {  // (inv holds only j < *n_idx <= sub.n_docs, or the sentinel)
-        sct_live(s.sub, j, o, n, err);
+        n = live_span(s.sub.offsets, s.sub.counts, j, o, err);
     } else {
         j = kSctNone;
-        sct_live(s.st, d, o, n, err);
+        n = live_span(s.st.offsets, s.st.counts, d, o, err);
     }
 }
 

@@ -32,14 +32,6 @@ struct SortWork {
     uint32_t* list;   // [n_docs] queued documents
 };
 
-// Live entries of doc d, clamped to its slots (a larger count is reported).
-__device__ __forceinline__ uint32_t sort_live(const BatchView& in, uint32_t d, uint32_t& err) {
-    const uint32_t slots = in.offsets[d + 1] - in.offsets[d];
-    const uint32_t n = live_count(in.offsets, in.counts, d);
-    if (n > slots) err |= kErrCapacity;
-    return n > slots ? slots : n;
-}
-
 // Sort the n <= EPL*64 entries at `keys` (element i = lane*EPL + q); returns
 // them with the index each came from.  Pads (i >= n) come last.
 template <int EPL>
@@ -89,8 +81,9 @@ __global__ __launch_bounds__(256) void sort_wave_kernel(BatchView in, OutView ou
     const uint32_t R = in.R;
     uint32_t err = 0;
     for (uint32_t d = uniform(blockIdx.x * 4 + (threadIdx.x >> 6)); d < in.n_docs; d += gridDim.x * 4) {
-        const uint32_t o = uniform(in.offsets[d]);
-        const uint32_t n = uniform(sort_live(in, d, err));
+        uint32_t o0;
+        const uint32_t n = uniform(live_span(in.offsets, in.counts, d, o0, err));
+        const uint32_t o = uniform(o0);
         if (n <= 64)
             err |= sort_doc_wave<1>(in, out, o, n, lane);
         else if (n <= 128)
@@ -138,9 +131,8 @@ __global__ __launch_bounds__(kSortNT) void sort_block_kernel(BatchView in, OutVi
         __syncthreads();  // every thread has read sh_slot before the next doc overwrites it
         if (slot >= total) break;
         const uint32_t d = sw.list[slot];
-        const uint32_t o = in.offsets[d];
-        uint32_t e0 = 0;
-        const uint32_t n = sort_live(in, d, e0);  // > kSortWaveMax (reported by the wave kernel)
+        uint32_t o, e0 = 0;
+        const uint32_t n = live_span(in.offsets, in.counts, d, o, e0);  // > kSortWaveMax (reported by the wave kernel)
         const uint32_t runs = (n + kSortWaveMax - 1) / kSortWaveMax;
         const uint32_t passes = 32u - (uint32_t)__clz(runs - 1u);
         // (key, index) ping-pong: an odd number of passes starts in the scratch

@@ -78,19 +78,6 @@ __device__ __forceinline__ uint32_t src_count_le(const uint32_t* a, uint32_t n, 
     return lo;
 }
 
-// Slot offset and live count of document d of one column set, the count clamped to the slots.
-__device__ __forceinline__ uint32_t src_live(const uint32_t* off, const uint32_t* cnt, uint32_t d, uint32_t& o,
-                                             uint32_t& err) {
-    o = 0;
-    if (!off) return 0u;
-    const uint32_t b = off[d], e = off[d + 1];
-    const uint32_t slots = e > b ? e - b : 0u;
-    const uint32_t live = cnt ? cnt[d] : slots;
-    if (live > slots) err |= kErrCapacity;
-    o = b;
-    return min(live, slots);
-}
-
 // The scan's LDS table, filled by the first thread with constant indices into the arguments.
 __device__ __forceinline__ void src_scan_table(const SourcesArgs& s, SrcScanRow* tab) {
     if (threadIdx.x == 0) {
@@ -119,8 +106,8 @@ __global__ __launch_bounds__(kSrcNT) void sources_count_kernel(SourcesArgs s, ui
         if (i < m) {
             const uint32_t src = base + i, d = src / s.n_reps, p = src - d * s.n_reps;
             uint32_t o;
-            me += src_live(tab[p].e_off, tab[p].e_cnt, d, o, err);
-            mt += src_live(tab[p].t_off, tab[p].t_cnt, d, o, err);
+            me += (tab[p].e_off ? live_span(tab[p].e_off, tab[p].e_cnt, d, o, err) : 0u);
+            mt += (tab[p].t_off ? live_span(tab[p].t_off, tab[p].t_cnt, d, o, err) : 0u);
         }
     }
 #pragma unroll
@@ -208,8 +195,8 @@ __global__ __launch_bounds__(kSrcNT) void sources_emit_kernel(SourcesArgs s, con
         if (i < m) {
             const uint32_t src = base + i, d = src / s.n_reps, p = src - d * s.n_reps;
             uint32_t o;
-            ce = src_live(tab[p].e_off, tab[p].e_cnt, d, o, err);
-            ct = src_live(tab[p].t_off, tab[p].t_cnt, d, o, err);
+            ce = tab[p].e_off ? live_span(tab[p].e_off, tab[p].e_cnt, d, o, err) : 0u;
+            ct = tab[p].t_off ? live_span(tab[p].t_off, tab[p].t_cnt, d, o, err) : 0u;
             const uint32_t* da = tab[p].doc_actor;
             s.out.src_actor[src] = da ? da[d] : tab[p].actor;
         }
@@ -277,7 +264,8 @@ __global__ __launch_bounds__(kSrcNT) void sources_gather_kernel(SourcesArgs s, u
         const uint32_t d = x / P;
         rp = x - d * P;
         uint32_t err = 0;  // (reported by sources_count_kernel)
-        n = src_live(tab[rp].off, tab[rp].cnt, d, so, err);
+        so = 0;
+        n = tab[rp].off ? live_span(tab[rp].off, tab[rp].cnt, d, so, err) : 0u;  // NULL: no such column set
     };
 
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {

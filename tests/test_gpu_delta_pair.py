@@ -286,6 +286,27 @@ def test_count_above_slots_is_clamped(eng, torch, which):
     same_docs(h2, want.ba, 4, 2, [0, 2, 3])
 
 
+@pytest.mark.parametrize("which", ["entries", "tombstones"])
+def test_count_above_slots_is_clamped_at_block_size(eng, torch, which):
+    """The same with 70 entries and 70 tombstones a side: the documents are the block
+    path's, which clamps the count again."""
+    rng = random.Random(6800)
+    docs = [pair_docs(rng, 2, 70, 70, 70, 70, m) for m in (0, 1, 2)]
+    a = make_replica(2, [p[0] for p in docs], actor=0, slack=1, with_counts=True)
+    b = make_replica(2, [p[1] for p in docs], actor=1, slack=1, with_counts=True)
+    assert not on_wave_path(a, b, 1)
+    cols = b.state if which == "entries" else b.tombs
+    cols.counts[1] = int(cols.offsets[2]) - int(cols.offsets[1]) + 9
+    got = exchange_on_device(eng, torch, a, b)
+    assert _code(eng.sync) == CRDT_E_CAPACITY
+    eng.sync()  # cleared
+    cols.counts[1] = int(cols.offsets[2]) - int(cols.offsets[1]) - 1
+    want = delta_pair_ref(a, b)
+    h1, h2 = host_out(got[0]), host_out(got[1])
+    same_docs(h1, want.ab, 3, 2, [0, 2])
+    same_docs(h2, want.ba, 3, 2, [0, 2])
+
+
 def test_argument_errors(eng, torch):
     """Every one of these is refused on the host: nothing is launched."""
     da, db = small_pair()

@@ -443,6 +443,26 @@ def test_count_above_slots_is_clamped(eng, torch):
         assert doc_lists(g, d) == doc_lists(want.log, d) and int(g["flags"][d]) == int(want.log["flags"][d]), d
 
 
+def test_count_above_slots_is_clamped_at_block_size(eng, torch):
+    """The same with 80 entries a side and the exchange: the document is the block path's,
+    which clamps the count again, as dst of one direction and as src of the other."""
+    dd, sd = small_pair(size=80)
+    a, b = pack(2, dd, slack=1), pack(2, sd, slack=1)
+    assert not on_wave_path(a, b, 1)
+    b.counts[1] = int(b.offsets[2]) - int(b.offsets[1]) + 9
+    o1, o2, l1, l2 = exchange_on_device(eng, torch, a, b)
+    assert _code(eng.sync) == CRDT_E_CAPACITY
+    eng.sync()  # cleared
+    b.counts[1] = int(b.offsets[2]) - int(b.offsets[1]) - 1
+    for (out, log), want in zip(((o1, l1), (o2, l2)), (join_log_ref(a, b), join_log_ref(b, a))):
+        h, g, hw = host_out(out), log.numpy(), want.out.as_batch()
+        for d in (0, 2, 3, 4, 5):
+            o, m = int(h.offsets[d]), int(h.counts[d])
+            live = list(zip(h.keys[o:o + m].tolist(), h.actors[o:o + m].tolist(), h.counters[o:o + m].tolist()))
+            assert live == hw.doc(d)[0], d
+            assert doc_lists(g, d) == doc_lists(want.log, d) and int(g["flags"][d]) == int(want.log["flags"][d]), d
+
+
 def test_argument_errors(eng, torch):
     """Every one of these is refused on the host: nothing is launched."""
     dd, sd = small_pair()

@@ -130,6 +130,18 @@ def test_sort_duplicate_in_each_path(eng, n):
     assert ei.value.code == crdtgpu.CRDT_E_DUP_KEY
 
 
+@pytest.mark.parametrize("n", [5, 300])
+def test_sort_count_above_slots_is_clamped(eng, n):
+    """A count above the document's slots, on the register path and on the merge-path
+    passes: clamped to the slots (nothing past them is read) and reported."""
+    rng = random.Random(n)
+    b = batch_of(2, [random_state(rng, 2, n, 10 ** 6, 9) for _ in range(3)], slack=1)
+    b.counts[1] = int(b.offsets[2]) - int(b.offsets[1]) + 9
+    with pytest.raises(crdtgpu.CrdtError) as ei:
+        eng.sort(b)
+    assert ei.value.code == crdtgpu.CRDT_E_CAPACITY
+
+
 def test_sort_large_doc_and_duplicates(eng):
     nrng = np.random.default_rng(2)
     n = 100_000
