@@ -23,6 +23,19 @@
 // state is then streamed once: every state entry and tombstone computes its
 // own output slot from the resolved keys (a lower bound in LDS plus prefix
 // counts), with no scan over the state.
+//
+// What a caller can rely on (tests/test_gpu_apply_edges.py):
+//   * offsets and counts (of out and of tomb_out) are written for every
+//     document.  A document whose op list is refused (more than 256 ops, an
+//     unknown kind, a DELTA_DEL_KEY outside a call or without a tomb_out, a
+//     clock bump with actor >= R) has count 0 in both; its slots and its clock
+//     are undefined; every other document of the batch is exact;
+//   * a live count above the document's slots, state or tombstones, is clamped
+//     to them and crdt_ctx_sync returns CRDT_E_CAPACITY, as in
+//     crdt_awset_has_async;
+//   * tomb_out == NULL: no tombstone is read or written, whatever `tombs`
+//     holds; Deleted is left as the caller holds it.
+// tomb_gc_kernel below has no status word: it takes counts[d] as given.
 #include "crdt_device.hpp"
 #include "wave_sort.hpp"
 
@@ -103,8 +116,11 @@ __global__ __launch_bounds__(WAVES * 64) void apply_kernel(BatchView st, TombVie
     for (uint32_t d = uniform(blockIdx.x * WAVES + w); d < n_docs; d += gridDim.x * WAVES) {
         const uint32_t o0 = ops.op_off[d], nops = ops.op_off[d + 1] - o0;
         const uint32_t actor = ops.doc_actor[d];
-        const uint32_t soff = st.offsets[d], ns = live_count(st.offsets, st.counts, d);
-        const uint32_t toff = tb.offsets ? tb.offsets[d] : 0u, nt = tb.offsets ? live_count(tb.offsets, tb.counts, d) : 0u;
+        // live prefixes clamped to the slots (kErrCapacity).  Without a tomb_out no
+        // tombstone is read or written (a DELTA_DEL_KEY is refused below): nt = 0
+        uint32_t soff, toff = 0;
+        const uint32_t ns = live_span(st.offsets, st.counts, d, soff, err);
+        const uint32_t nt = has_tout && tb.offsets ? live_span(tb.offsets, tb.counts, d, toff, err) : 0u;
         const uint32_t obase = soff + o0, tbase = toff + o0;
         // slot bounds of every doc (outputs are valid input batches)
         if (lane == 0) {
@@ -115,8 +131,16 @@ __global__ __launch_bounds__(WAVES * 64) void apply_kernel(BatchView st, TombVie
                 if (d == n_docs - 1) tout.offsets[n_docs] = tend_off;
             }
         }
-        if (nops > kApplyMaxOps) {  // one call holds at most 256 ops per doc (outputs of d undefined)
+        // a refused doc comes out empty: counts 0 (its entries and clock are undefined)
+        const auto refuse = [&] {
+            if (lane == 0) {
+                out.counts[d] = 0;
+                if (has_tout) tout.counts[d] = 0;
+            }
+        };
+        if (nops > kApplyMaxOps) {  // one call holds at most 256 ops per doc
             err |= kErrHint;
+            refuse();
             continue;
         }
         uint32_t derr = 0;
@@ -154,8 +178,9 @@ __global__ __launch_bounds__(WAVES * 64) void apply_kernel(BatchView st, TombVie
                 if (bump[q] && actor >= R) derr |= kErrActorRange;  // VersionVector[actor]++ out of range
             }
         }
-        if (ballot(derr != 0)) {  // the reference panics (or the ops are malformed): outputs of d undefined
+        if (ballot(derr != 0)) {  // the reference panics (or the ops are malformed)
             err |= derr;
+            refuse();
             wave_sync();
             continue;
         }

@@ -90,6 +90,26 @@ def make_case(rng, n_docs, R, state_size, ops_size, universe=300, max_c=40, tomb
     return AWSetBatch.from_docs(R, docs), TombBatch.from_lists(tombs), OpBatch.from_lists(per_ops, actors), want
 
 
+STALE_KEY = 1  # what input slack holds: below every live key, so a slot read past a count breaks the order
+
+
+def tomb_batch(lists, slack=0):
+    """A TombBatch of the lists; slack > 0: that many stale slots behind each list, with counts."""
+    tb = TombBatch.from_lists(lists)
+    if not slack:
+        return tb
+    counts = np.array([len(x) for x in lists], np.uint32)
+    off = np.zeros(len(lists) + 1, np.uint32)
+    np.cumsum(counts + np.uint32(slack), out=off[1:])
+    n = int(off[-1])
+    k, a, c = np.full(n, STALE_KEY, np.uint64), np.full(n, 2, np.uint32), np.full(n, 99, np.uint64)
+    for d, lst in enumerate(lists):
+        o = int(off[d])
+        for i, (kk, aa, cc) in enumerate(lst):
+            k[o + i], a[o + i], c[o + i] = kk, aa, cc
+    return TombBatch(off, k, a, c, counts=counts)
+
+
 def doc_of(out, tout, d, R):
     o, n = int(out.offsets[d]), int(out.counts[d])
     e = list(zip(out.keys[o:o + n].tolist(), out.actors[o:o + n].tolist(), out.counters[o:o + n].tolist()))
