@@ -231,6 +231,10 @@ def signatures():
         "crdt_awset_delta_join_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CReplica), P(CAWSetOut), _vp, _vp]),
         "crdt_awset_delta_exchange_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), P(CAWSetOut), P(CAWSetOut),
                                                            _vp, _vp, _vp]),
+        "crdt_awset_delta_join_log_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CReplica), P(CAWSetOut), _vp,
+                                                           P(CMergeLog), _vp]),
+        "crdt_awset_delta_exchange_log_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), P(CAWSetOut), P(CAWSetOut),
+                                                               _vp, _vp, P(CMergeLog), P(CMergeLog), _vp]),
         "crdt_replica_select_async": (ctypes.c_int, [_vp, P(CReplica), _vp, _vp, _u32, _u32, _u32, P(CReplicaOut), _vp]),
         "crdt_replica_scatter_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), _vp, _vp, _u32, _u32,
                                                       P(CReplicaOut), _vp]),

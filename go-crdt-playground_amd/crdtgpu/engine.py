@@ -343,6 +343,55 @@ class Engine:
             host.append(h)
         return host[0], host[1], _np(kinds[0], np.uint8)[:n], _np(kinds[1], np.uint8)[:n]
 
+    def delta_join_log_async(self, dst: AWSetBatch, src, out: OutBuffers, log: MergeLogBuffers, kind=None,
+                             stream=None):
+        """delta_join_async with the merge's log written beside the merged state: per doc, the
+        dst entries removed (in dst's slot layout) and the src entries added or moved to (in
+        src's), with CRDT_DIFF_* flags and the summary -- what diff_async(dst, out) reports,
+        from the one read the merge needs (crdt_awset_delta_join_log_async)."""
+        d, s, o, lg = _c(dst), _c(src), _c(out), _c(log)
+        check(self._lib.crdt_awset_delta_join_log_async(self._ctx, ctypes.byref(d), ctypes.byref(s), ctypes.byref(o),
+                                                        ptr(kind), ctypes.byref(lg), _stream(stream)),
+              "crdt_awset_delta_join_log_async")
+
+    def delta_exchange_log_async(self, a, b, out_ab: OutBuffers, out_ba: OutBuffers, log_ab: MergeLogBuffers,
+                                 log_ba: MergeLogBuffers, kind_ab=None, kind_ba=None, stream=None):
+        """delta_exchange_async with both directions' logs, from one read of both replicas:
+        log_ab removed in a's layout and upserted in b's, log_ba the other way round
+        (crdt_awset_delta_exchange_log_async)."""
+        ca, cb, o1, o2, l1, l2 = _c(a), _c(b), _c(out_ab), _c(out_ba), _c(log_ab), _c(log_ba)
+        check(self._lib.crdt_awset_delta_exchange_log_async(self._ctx, ctypes.byref(ca), ctypes.byref(cb),
+                                                            ctypes.byref(o1), ctypes.byref(o2), ptr(kind_ab),
+                                                            ptr(kind_ba), ctypes.byref(l1), ctypes.byref(l2),
+                                                            _stream(stream)),
+              "crdt_awset_delta_exchange_log_async")
+
+    def delta_exchange_log(self, a, b):
+        """Host replicas uploaded, exchanged with the logs on the device and downloaded:
+        (out_ab, out_ba, kind_ab, kind_ba, log_ab, log_ba), the outputs as host OutBuffers, the
+        kinds as numpy uint8 arrays and the logs as MergeLogBuffers.numpy() (for tests and
+        small callers)."""
+        import numpy as np
+        import torch
+
+        a, b = a.numpy(), b.numpy()
+        n, R = a.n_docs, a.state.R
+        sa, sb = int(a.state.offsets[-1]), int(b.state.offsets[-1])
+        dev = torch.device("cuda", self.device)
+        outs = [OutBuffers(n, R, sa + sb, device=dev) for _ in range(2)]
+        kinds = [torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) for _ in range(2)]
+        logs = [MergeLogBuffers(n, sa, sb, device=dev), MergeLogBuffers(n, sb, sa, device=dev)]
+        self.delta_exchange_log_async(a.to(dev), b.to(dev), outs[0], outs[1], logs[0], logs[1], kinds[0], kinds[1])
+        self.sync()
+        host = []
+        for o in outs:
+            h = OutBuffers(n, R, sa + sb)
+            h.offsets, h.counts, h.vv = _np(o.offsets, np.uint32), _np(o.counts, np.uint32), _np(o.vv, np.uint64)
+            h.keys, h.actors, h.counters = _np(o.keys, np.uint64), _np(o.actors, np.uint32), _np(o.counters, np.uint64)
+            host.append(h)
+        return (host[0], host[1], _np(kinds[0], np.uint8)[:n], _np(kinds[1], np.uint8)[:n], logs[0].numpy(),
+                logs[1].numpy())
+
     def replica_select_async(self, rep, out: ReplicaBuffers, idx=None, n_idx=None, n_out=None, entry_slots=None,
                              tomb_slots=None, stream=None):
         """select_async over a whole resident Replica: out doc j = rep doc idx[j] for

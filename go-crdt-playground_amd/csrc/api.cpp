@@ -67,6 +67,10 @@ size_t join_log_parts_bytes();
 hipError_t launch_join_log(const BatchView& A, const BatchView& B, const OutView& out_ab, const OutView* out_ba,
                            const MergeLogView& log_ab, const MergeLogView* log_ba, const Work& wk, uint32_t* parts,
                            uint32_t block_grid, hipStream_t stream);
+hipError_t launch_delta_pair_log(const PairSide& A, const PairSide& B, const OutView& out_ab, const OutView* out_ba,
+                                 uint8_t* kind_ab, uint8_t* kind_ba, const MergeLogView& log_ab,
+                                 const MergeLogView* log_ba, const Work& wk, uint32_t* parts, uint32_t block_grid,
+                                 hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
                          uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
@@ -1249,6 +1253,146 @@ int crdt_awset_exchange_log_async(crdt_ctx* ctx, const crdt_awset_batch* a, cons
                                   const crdt_merge_log* log_ab, const crdt_merge_log* log_ba, void* stream) {
     if (!out_ba || !log_ba) return CRDT_E_INVALID;
     return join_log_common(ctx, a, b, out_ab, out_ba, log_ab, log_ba, stream);
+}
+
+// Logged delta merge of a resident pair (delta_pair_log.hip).  Workspace: the
+// join's worklist and the summary's partial sums, as the logged join.  The
+// argument errors are the delta exchange's and the logged join's together.
+// a_tombs / a_doc_actor / a_actor: replica a beyond its state (the exchange);
+// out_ba / log_ba == NULL: the join, which reads none of them.
+static int delta_pair_log_common(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_tomb_batch* a_tombs,
+                                 const uint32_t* a_doc_actor, uint32_t a_actor, const crdt_replica* b,
+                                 const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
+                                 uint8_t* kind_ba, const crdt_merge_log* log_ab, const crdt_merge_log* log_ba,
+                                 void* stream) {
+    if (!ctx || !batch_ptrs_ok(a) || !b || !batch_ptrs_ok(b->state) || !out_ptrs_ok(out_ab) ||
+        (out_ba && !out_ptrs_ok(out_ba)))
+        return CRDT_E_INVALID;
+    const crdt_awset_batch* bs = b->state;
+    if (a->n_docs != bs->n_docs || a->R != bs->R) return CRDT_E_INVALID;
+    if ((a_tombs && !a_tombs->offsets) || (b->tombs && !b->tombs->offsets)) return CRDT_E_INVALID;
+    const crdt_merge_log* const logs[2] = {log_ab, log_ba};
+    const int n_logs = out_ba ? 2 : 1;
+    for (int i = 0; i < n_logs; ++i) {
+        const crdt_merge_log* l = logs[i];
+        if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
+            !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
+            return CRDT_E_INVALID;
+    }
+    // No two written arrays start at one address, the per-document arrays, whose
+    // sizes the host knows, do not overlap at all, and no written array starts
+    // where an input array of the same kind starts.
+    const size_t n = a->n_docs, R = a->R;
+    struct Range {
+        uintptr_t p;
+        size_t bytes;  // 0: size unknown here (entry arrays)
+        int width;     // bytes per element: the array's kind
+    };
+    std::vector<Range> r;
+    for (const crdt_awset_out* o : {out_ab, out_ba}) {
+        if (!o) continue;
+        r.push_back({(uintptr_t)o->offsets, (n + 1) * 4, 4});
+        r.push_back({(uintptr_t)o->counts, n * 4, 4});
+        r.push_back({(uintptr_t)o->vv, n * R * 8, 8});
+        r.push_back({(uintptr_t)o->keys, 0, 8});
+        r.push_back({(uintptr_t)o->actors, 0, 4});
+        r.push_back({(uintptr_t)o->counters, 0, 8});
+    }
+    for (int i = 0; i < n_logs; ++i) {
+        const crdt_merge_log* l = logs[i];
+        r.push_back({(uintptr_t)l->flags, n, 1});
+        if (l->summary) r.push_back({(uintptr_t)l->summary, 5 * 4, 4});
+        r.push_back({(uintptr_t)l->rem_offsets, (n + 1) * 4, 4});
+        r.push_back({(uintptr_t)l->rem_counts, n * 4, 4});
+        r.push_back({(uintptr_t)l->ups_offsets, (n + 1) * 4, 4});
+        r.push_back({(uintptr_t)l->ups_counts, n * 4, 4});
+        r.push_back({(uintptr_t)l->rem_keys, 0, 8});
+        r.push_back({(uintptr_t)l->rem_actors, 0, 4});
+        r.push_back({(uintptr_t)l->rem_counters, 0, 8});
+        r.push_back({(uintptr_t)l->ups_keys, 0, 8});
+        r.push_back({(uintptr_t)l->ups_actors, 0, 4});
+        r.push_back({(uintptr_t)l->ups_counters, 0, 8});
+        if (l->ups_kind) r.push_back({(uintptr_t)l->ups_kind, 0, 1});
+    }
+    if (kind_ab) r.push_back({(uintptr_t)kind_ab, n, 1});
+    if (out_ba && kind_ba) r.push_back({(uintptr_t)kind_ba, n, 1});
+    for (size_t i = 0; i < r.size(); ++i)
+        for (size_t j = i + 1; j < r.size(); ++j) {
+            if (r[i].p == r[j].p) return CRDT_E_INVALID;
+            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
+                return CRDT_E_INVALID;
+        }
+    const crdt_tomb_batch* tb[2] = {a_tombs, b->tombs};
+    const crdt_awset_batch* st[2] = {a, bs};
+    const uint32_t* da[2] = {a_doc_actor, b->doc_actor};
+    for (int p = 0; p < 2; ++p)
+        for (const Range& w : r) {
+            if (w.width == 4) {
+                if (w.p == (uintptr_t)st[p]->offsets || w.p == (uintptr_t)st[p]->counts ||
+                    w.p == (uintptr_t)st[p]->actors || (da[p] && w.p == (uintptr_t)da[p]))
+                    return CRDT_E_INVALID;
+                if (tb[p] && (w.p == (uintptr_t)tb[p]->offsets || (tb[p]->counts && w.p == (uintptr_t)tb[p]->counts) ||
+                              (tb[p]->actors && w.p == (uintptr_t)tb[p]->actors)))
+                    return CRDT_E_INVALID;
+            }
+            if (w.width == 8) {
+                if (w.p == (uintptr_t)st[p]->keys || w.p == (uintptr_t)st[p]->counters || w.p == (uintptr_t)st[p]->vv)
+                    return CRDT_E_INVALID;
+                if (tb[p] && ((tb[p]->keys && w.p == (uintptr_t)tb[p]->keys) ||
+                              (tb[p]->counters && w.p == (uintptr_t)tb[p]->counters)))
+                    return CRDT_E_INVALID;
+            }
+        }
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (rc != CRDT_OK) return rc;
+    if (a->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
+    auto side = [](const crdt_awset_batch* st_, const crdt_tomb_batch* t, const uint32_t* doc_actor, uint32_t actor) {
+        PairSide ps{};
+        ps.st = view(st_);
+        if (t) ps.tb = TombView{t->offsets, t->counts, t->keys, t->actors, t->counters};
+        ps.doc_actor = doc_actor;
+        ps.actor = actor;
+        return ps;
+    };
+    auto lview = [](const crdt_merge_log* l) {
+        return MergeLogView{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
+                            l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
+                            l->ups_actors, l->ups_counters, l->ups_kind};
+    };
+    OutView o2v;
+    MergeLogView l2v;
+    if (out_ba) {
+        o2v = view(out_ba);
+        l2v = lview(log_ba);
+    }
+    rc = hip_err(launch_delta_pair_log(side(a, a_tombs, a_doc_actor, a_actor),
+                                       side(bs, b->tombs, b->doc_actor, b->actor), view(out_ab),
+                                       out_ba ? &o2v : nullptr, kind_ab, kind_ba, lview(log_ab),
+                                       out_ba ? &l2v : nullptr, make_work(ctx), ctx->parts.as<uint32_t>(),
+                                       block_grid(ctx), s));
+    return leave(ctx, s, cap, rc);
+}
+
+int crdt_awset_delta_join_log_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
+                                    const crdt_awset_out* out, uint8_t* kind, const crdt_merge_log* log,
+                                    void* stream) {
+    return delta_pair_log_common(ctx, dst, nullptr, nullptr, 0u, src, out, nullptr, kind, nullptr, log, nullptr,
+                                 stream);
+}
+
+int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, const crdt_replica* b,
+                                        const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
+                                        uint8_t* kind_ba, const crdt_merge_log* log_ab, const crdt_merge_log* log_ba,
+                                        void* stream) {
+    if (!a || !out_ba || !log_ba) return CRDT_E_INVALID;
+    return delta_pair_log_common(ctx, a->state, a->tombs, a->doc_actor, a->actor, b, out_ab, out_ba, kind_ab,
+                                 kind_ba, log_ab, log_ba, stream);
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,

@@ -39,12 +39,7 @@ constexpr int kPairWaves = 4;      // wavefronts (= documents) per workgroup of 
 constexpr int kPairWaveMax = 64;   // live entries, and live tombstones, per side the wave path takes
 constexpr int kPairBlockNT = 256;  // block path: threads per workgroup
 constexpr int kPairBlockIPT = 4;   // block path: merged positions per thread and window
-
-// Per wave: the entries and clocks (merge_wave.hpp) and both sides' tombstones.
-struct PairWaveSmem : WaveSmem {
-    uint64_t tk[2][64], tc[2][64];
-    uint32_t ta[2][64];
-};
+// (PairWaveSmem and the kind of a direction: merge_wave.hpp, shared with delta_pair_log.hip)
 
 // One direction of a wave-path document: dst = side x of sm, src = side 1 - x.
 __device__ __forceinline__ void pair_wave_dir(const PairWaveSmem& sm, uint32_t x, uint32_t nd, uint32_t ns,
@@ -56,20 +51,8 @@ __device__ __forceinline__ void pair_wave_dir(const PairWaveSmem& sm, uint32_t x
     const Entries tomb{sm.tk[y], sm.ta[y], sm.tc[y], nts};
 
     // the kind, before any entry is decided (:53, :60)
-    const bool full = uniform((uint32_t)(vv_counter(p.dvv, R, s_actor, err) == 0ull)) != 0u;
-    uint32_t kind = CRDT_DELTA_FULL;
-    if (!full) {
-        const bool changed = p.sv && !has_dot(p.dvv, R, p.Sa, p.Sc, err);
-        bool effective = false;  // a tombstone the re-add filter lets through (:93-102)
-        if (lane < nts) {
-            const uint64_t Tk = sm.tk[y][lane];
-            const uint32_t m = lower_bound_pow<6>(p.sk, ns, Tk);
-            const bool readded = m < ns && p.sk[m & 63] == Tk &&
-                                 (sm.ea[y][m & 63] != sm.ta[y][lane] || sm.ec[y][m & 63] > sm.tc[y][lane]);
-            effective = !readded;
-        }
-        kind = (ballot(changed) | ballot(effective)) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
-    }
+    bool full;
+    const uint32_t kind = pair_wave_kind(sm, p, y, ns, nts, s_actor, R, lane, full, err);
 
     bool dkeep = false, skeep = false;
     uint32_t oda = p.Da, osa = p.Sa;

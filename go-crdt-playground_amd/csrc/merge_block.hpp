@@ -8,8 +8,8 @@
 //
 // The walk exists once (merge_walk).  What it writes is its sink's business:
 // block_merge places the survivors (KeepSink: join.hip, fold.hip, delta_pair.hip);
-// the logged join adds the removed and upserted records beside them (LogSink,
-// join_log.hip).  The file also holds what the four block kernels share around
+// the logged merges add the removed and upserted records beside them (LogSink,
+// merge_log.hpp: join_log.hip, delta_pair_log.hip).  The file also holds what the block kernels share around
 // the walk: the worklist loop (for_each_work) and the test whether a delta source
 // changes anything (delta_changes).
 //
@@ -173,7 +173,8 @@ struct KeepSink {
 // whole workgroup.  sm.dvv / sm.svv must hold the two version vectors.  Each
 // window's positions are classified (kPos*) and handed to sink.place with the key
 // and the dot their record carries: the merged dot of a survivor, and of a dropped
-// dst entry its own, which decide returns too.
+// dst entry its own (a logging sink is handed dst's dot even where delta mode moved
+// the common key to src's dot before a tombstone dropped it).
 //
 // A common key is classified where its dst entry is taken, which always sees the
 // src entry (the src window reaches a whole window ahead), so a pair that
@@ -232,7 +233,16 @@ __device__ void merge_walk(const Entries& D, const Entries& S, const Entries& to
                                            oc[q], err);
                     ok[q] = key;
                     cls[q] = kp ? kPosKeep : kPosRem;
-                    if (Sink::kLog && match && (oa[q] != d_a || oc[q] != d_c)) cls[q] |= kPosUpd;
+                    if (Sink::kLog) {
+                        // UPDATED only on a kept key; a dropped entry's record carries dst's own dot.
+                        // (Delta mode can move a common key to src's dot and then drop it by a
+                        // tombstone; in full mode a common key is never dropped.)
+                        if (kp && match && (oa[q] != d_a || oc[q] != d_c)) cls[q] |= kPosUpd;
+                        if (!kp) {
+                            oa[q] = d_a;
+                            oc[q] = d_c;
+                        }
+                    }
                     ++a;
                 } else {
                     const uint64_t key = sm.sk[b];

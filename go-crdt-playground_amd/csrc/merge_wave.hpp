@@ -115,6 +115,37 @@ __device__ __forceinline__ void wave_clock(const WaveDir& p, bool keep_dst, cons
     }
 }
 
+// ---- the delta merges (delta_pair.hip, delta_pair_log.hip): tombstones and the kind.
+// Per wave: the entries and clocks and both sides' tombstones (<= 64 a side).
+struct alignas(8) PairWaveSmem : WaveSmem {
+    alignas(8) uint64_t tk[2][64];
+    alignas(8) uint64_t tc[2][64];
+    uint32_t ta[2][64];
+};
+
+// The kind of the direction p of a staged document, before any entry is decided
+// (awset-delta_test.go:53, :60): src = side y with ns entries, nts tombstones and
+// actor s_actor.  full: D has never met src's actor.
+__device__ __forceinline__ uint32_t pair_wave_kind(const PairWaveSmem& sm, const WaveDir& p, uint32_t y, uint32_t ns,
+                                                   uint32_t nts, uint32_t s_actor, uint32_t R, uint32_t lane,
+                                                   bool& full, uint32_t& err) {
+    full = uniform((uint32_t)(vv_counter(p.dvv, R, s_actor, err) == 0ull)) != 0u;
+    uint32_t kind = CRDT_DELTA_FULL;
+    if (!full) {
+        const bool changed = p.sv && !has_dot(p.dvv, R, p.Sa, p.Sc, err);
+        bool effective = false;  // a tombstone the re-add filter lets through (:93-102)
+        if (lane < nts) {
+            const uint64_t Tk = sm.tk[y][lane];
+            const uint32_t m = lower_bound_pow<6>(p.sk, ns, Tk);
+            const bool readded = m < ns && p.sk[m & 63] == Tk &&
+                                 (sm.ea[y][m & 63] != sm.ta[y][lane] || sm.ec[y][m & 63] > sm.tc[y][lane]);
+            effective = !readded;
+        }
+        kind = (ballot(changed) | ballot(effective)) ? CRDT_DELTA_DELTA : CRDT_DELTA_NONE;
+    }
+    return kind;
+}
+
 // Slot bounds of one direction's outputs for document d, from the inputs' own
 // (dst's slots start at doff, src's at soff): the merged state's, and the logged
 // join's two lists (a removed entry was a dst entry, an upserted one a src entry;

@@ -812,6 +812,93 @@ func (e *Engine) ExchangeLog(a, b *C.crdt_awset_batch, outAB, outBA *C.crdt_awse
 	return nil
 }
 
+// ---------------------------------------------------------------- delta merge of a resident pair
+
+// DeltaJoin is (*AWSetDelta).Merge on resident replicas as they stand
+// (crdt_awset_delta_join_async): out[d] = dst[d] <- src[d], in the join's layout.
+// dst is a plain state (the destination's tombstones and actor are not read); kind,
+// a device array of one byte per document or nil, receives CRDT_DELTA_FULL / DELTA /
+// NONE. Asynchronous on stream; device-side errors surface at the context's next sync.
+func (e *Engine) DeltaJoin(dst *C.crdt_awset_batch, src *Replica, out *C.crdt_awset_out, kind *C.uint8_t,
+	stream unsafe.Pointer) error {
+	if dst == nil || src == nil || out == nil {
+		return fmt.Errorf("DeltaJoin: nil argument")
+	}
+	var a arena
+	defer a.free()
+	cs := replicaC(&a, src)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_awset_delta_join_async(e.ctx, dst, cs, out, kind, stream); rc != 0 {
+		return errOf("crdt_awset_delta_join_async", rc)
+	}
+	return nil
+}
+
+// DeltaExchange is both delta merges of a resident pair from one read of both
+// (crdt_awset_delta_exchange_async): outAB = a <- b and outBA = b <- a. kindAB and
+// kindBA are device arrays of one byte per document, or nil.
+func (e *Engine) DeltaExchange(ra, rb *Replica, outAB, outBA *C.crdt_awset_out, kindAB, kindBA *C.uint8_t,
+	stream unsafe.Pointer) error {
+	if ra == nil || rb == nil || outAB == nil || outBA == nil {
+		return fmt.Errorf("DeltaExchange: nil argument")
+	}
+	var a arena
+	defer a.free()
+	ca, cb := replicaC(&a, ra), replicaC(&a, rb)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_awset_delta_exchange_async(e.ctx, ca, cb, outAB, outBA, kindAB, kindBA, stream); rc != 0 {
+		return errOf("crdt_awset_delta_exchange_async", rc)
+	}
+	return nil
+}
+
+// DeltaJoinLog is DeltaJoin with the merge's decision log written beside the merged
+// state from the same read (crdt_awset_delta_join_log_async): log's removed list of
+// document d starts at dst.offsets[d], its upserted list at src's offsets[d]. A NONE
+// document has empty lists and flags 0; a common key that the delta merge moves to
+// src's dot and a tombstone then removes is recorded as removed with dst's dot.
+func (e *Engine) DeltaJoinLog(dst *C.crdt_awset_batch, src *Replica, out *C.crdt_awset_out, kind *C.uint8_t,
+	log *MergeLog, stream unsafe.Pointer) error {
+	if dst == nil || src == nil || out == nil || log == nil {
+		return fmt.Errorf("DeltaJoinLog: nil argument")
+	}
+	var a arena
+	defer a.free()
+	cs := replicaC(&a, src)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_awset_delta_join_log_async(e.ctx, dst, cs, out, kind, &log.Log, stream); rc != 0 {
+		return errOf("crdt_awset_delta_join_log_async", rc)
+	}
+	return nil
+}
+
+// DeltaExchangeLog is DeltaExchange with both directions' logs
+// (crdt_awset_delta_exchange_log_async): logAB's removed list is in a's layout and
+// its upserted list in b's, logBA's the other way round.
+func (e *Engine) DeltaExchangeLog(ra, rb *Replica, outAB, outBA *C.crdt_awset_out, kindAB, kindBA *C.uint8_t,
+	logAB, logBA *MergeLog, stream unsafe.Pointer) error {
+	if ra == nil || rb == nil || outAB == nil || outBA == nil || logAB == nil || logBA == nil {
+		return fmt.Errorf("DeltaExchangeLog: nil argument")
+	}
+	var a arena
+	defer a.free()
+	ca, cb := replicaC(&a, ra), replicaC(&a, rb)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_awset_delta_exchange_log_async(e.ctx, ca, cb, outAB, outBA, kindAB, kindBA, &logAB.Log,
+		&logBA.Log, stream); rc != 0 {
+		return errOf("crdt_awset_delta_exchange_log_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- state digests
 
 // HostBatch is a packed batch in host memory: State as arena.batch lays it out

@@ -973,6 +973,69 @@ int crdt_awset_delta_exchange_async(crdt_ctx* ctx, const crdt_replica* a, const 
                                     const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
                                     uint8_t* kind_ab, uint8_t* kind_ba /* each [n_docs] or NULL */, void* stream);
 
+/* ---- logged delta merge: the delta merge with its decision log ----------------
+ * The two calls above with the log of crdt_awset_join_log_async beside them: who
+ * keeps an index, a view or a feed beside the sets learns what a delta merge
+ * changed without crdt_awset_diff_async's second read of both batches and its
+ * search per key.  The delta merge's kernels have made every one of those
+ * decisions when they write the merged state.
+ * The merged state: out (out_ab, out_ba) and kind (kind_ab, kind_ba) hold what
+ * crdt_awset_delta_join_async (crdt_awset_delta_exchange_async) writes for the
+ * same inputs -- live entries, counts, offsets, clocks and kinds bit for bit,
+ * document d at a.offsets[d] + b.offsets[d], slack unspecified.
+ * The log of direction dst <- src is crdt_awset_diff_async(dst, out)'s answer in
+ * the logged join's layout (crdt_merge_log, above): removed records at
+ * dst.offsets[d], rem_offsets repeating dst's slot bounds; upserted records at
+ * src.offsets[d], ups_offsets repeating src's; each list in key order and a valid
+ * crdt_tomb_batch as it stands; flags[d] and the five words of summary as there.
+ * By the kind of the direction (awset-delta_test.go:51-166):
+ *   CRDT_DELTA_FULL   exactly the log crdt_awset_join_log_async writes.
+ *   CRDT_DELTA_NONE   both lists empty and flags[d] == 0: CRDT_DIFF_CLOCK stays
+ *                     clear even when src's clock is ahead, because the clock is
+ *                     not merged (:60).  The document adds nothing to summary.
+ *   CRDT_DELTA_DELTA  - a dst-only key is removed only by an effective tombstone
+ *                       of src whose dot D has not seen (:149-164); never because
+ *                       S covers its dot.
+ *                     - a src-only key is ADDED when D has not seen its dot and no
+ *                       such tombstone removes it again in phase 2; when one does,
+ *                       there is no record at all.
+ *                     - a common key is UPDATED when D has not seen s's dot and the
+ *                       key survives.
+ *                     - a common key that phase 1 moves to s's dot and phase 2 then
+ *                       removes (src holds (x, c) and a tombstone (x, c' >= c) of
+ *                       it, D[x] < c) is recorded as removed WITH THE DOT IT HAD IN
+ *                       DST, and has no upsert record.
+ *                     - a tombstone of a key neither side holds leaves no record;
+ *                       the document is still DELTA, and CRDT_DIFF_CLOCK is set iff
+ *                       out.vv[d] != dst.vv[d].
+ * Exchange: both directions from one read.  log_ab.removed is in a's layout and
+ * log_ab.upserted in b's; log_ba.removed is in b's layout and log_ba.upserted in
+ * a's.  Slots of a list at or past its count are unspecified; slots of other
+ * documents are never written.  The bits are the same on every run.
+ * Reported by crdt_ctx_sync: as the delta merge above (CRDT_E_ACTOR_RANGE on
+ * Counter(s) at s == R and on any HasDot the chosen path evaluates at actor == R;
+ * CRDT_E_CAPACITY on a live count above its slots, clamped).
+ * Returned by the call (CRDT_E_INVALID): the delta merge's and the logged join's
+ * argument errors together -- a NULL argument or required field (summary,
+ * ups_kind and the kind pointers may be NULL); an n_docs or R mismatch; R out of
+ * range; a tomb batch without offsets; two written arrays (outputs, log arrays,
+ * kinds) starting at one address or overlapping per-document arrays; a written
+ * array starting where an input array of the same kind (state, tombstones,
+ * doc_actor) starts.
+ * n_docs == 0 launches nothing that reads documents; summary, when given, is
+ * zeroed.  Ordered after the context's previous call; no host sync, kernel nodes
+ * only, capturable.  Workspace: the join's worklist, one word per document, sized
+ * by crdt_ctx_reserve(max_docs, ..); CRDT_E_WORKSPACE when it would have to grow
+ * during a graph capture; and the logged join's fixed 64 KB of summary partial
+ * sums.  There is no _batch form. */
+int crdt_awset_delta_join_log_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
+                                    const crdt_awset_out* out, uint8_t* kind /* [n_docs] or NULL */,
+                                    const crdt_merge_log* log, void* stream);
+int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, const crdt_replica* b,
+                                        const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
+                                        uint8_t* kind_ab, uint8_t* kind_ba /* each [n_docs] or NULL */,
+                                        const crdt_merge_log* log_ab, const crdt_merge_log* log_ba, void* stream);
+
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
  * that packs Go maps (random iteration order) can hand them over unsorted and
