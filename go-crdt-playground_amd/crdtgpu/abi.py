@@ -235,6 +235,8 @@ def signatures():
                                                            P(CMergeLog), _vp]),
         "crdt_awset_delta_exchange_log_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), P(CAWSetOut), P(CAWSetOut),
                                                                _vp, _vp, P(CMergeLog), P(CMergeLog), _vp]),
+        "crdt_awset_fold_log_async": (ctypes.c_int, [_vp, ctypes.c_int, P(CAWSetBatch), P(CSrcBatch), P(CAWSetOut),
+                                                     P(CMergeLog), _vp]),
         "crdt_replica_select_async": (ctypes.c_int, [_vp, P(CReplica), _vp, _vp, _u32, _u32, _u32, P(CReplicaOut), _vp]),
         "crdt_replica_scatter_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), _vp, _vp, _u32, _u32,
                                                       P(CReplicaOut), _vp]),

@@ -212,6 +212,42 @@ class Engine:
         h.keys, h.actors, h.counters = _np(out.keys, np.uint64), _np(out.actors, np.uint32), _np(out.counters, np.uint64)
         return h, log.numpy()
 
+    def fold_log_async(self, mode: int, dst: AWSetBatch, srcs: SrcBatch, out: OutBuffers, log: MergeLogBuffers,
+                       stream=None):
+        """fold_async with the log of the whole ordered fold beside the merged state: per doc,
+        the dst entries that are gone at the end (at dst.offsets[d]) and the entries that are
+        new or under another dot at the end (at entry_off[doc_srcs[d]], capacity the sources'
+        entry slots) -- what diff_async(dst, out) reports; steps in between do not show
+        (crdt_awset_fold_log_async)."""
+        d, s, o, lg = _c(dst), _c(srcs), _c(out), _c(log)
+        check(self._lib.crdt_awset_fold_log_async(self._ctx, int(mode), ctypes.byref(d), ctypes.byref(s),
+                                                  ctypes.byref(o), ctypes.byref(lg), _stream(stream)),
+              "crdt_awset_fold_log_async")
+
+    def fold_log(self, mode: int, dst: AWSetBatch, srcs: SrcBatch):
+        """Host batches uploaded, folded with the log on the device and downloaded: (the merged
+        state as host OutBuffers, the log as host MergeLogBuffers), both sized from the inputs
+        (for tests and small callers)."""
+        import numpy as np
+        import torch
+
+        dst, srcs = dst.numpy(), srcs.numpy()
+        n, R = dst.n_docs, dst.R
+        ds, es = int(dst.offsets[-1]), int(srcs.entry_off[-1])
+        dev = torch.device("cuda", self.device)
+        out = OutBuffers(n, R, ds + es, device=dev)
+        log = MergeLogBuffers(n, ds, es, device=dev)
+        self.reserve(n, ds + es)
+        self.fold_log_async(mode, dst.to(dev), srcs.to(dev), out, log)
+        self.sync()
+        h = OutBuffers(n, R, ds + es)
+        h.offsets, h.counts, h.vv = _np(out.offsets, np.uint32), _np(out.counts, np.uint32), _np(out.vv, np.uint64)
+        h.keys, h.actors, h.counters = _np(out.keys, np.uint64), _np(out.actors, np.uint32), _np(out.counters, np.uint64)
+        hl = MergeLogBuffers(n, ds, es)
+        for f, a in log.numpy().items():
+            setattr(hl, f, a)
+        return h, hl
+
     def digest_async(self, state: AWSetBatch, out, tombs: TombBatch = None, stream=None):
         """Per doc, the 16-byte digest of its live state into `out` (device u64 [2 * n_docs]):
         word 0 the element set, word 1 elements, dots, Deleted and clock

@@ -71,6 +71,9 @@ hipError_t launch_delta_pair_log(const PairSide& A, const PairSide& B, const Out
                                  uint8_t* kind_ab, uint8_t* kind_ba, const MergeLogView& log_ab,
                                  const MergeLogView* log_ba, const Work& wk, uint32_t* parts, uint32_t block_grid,
                                  hipStream_t stream);
+hipError_t launch_fold_log(int mode, const BatchView& dst, const SrcView& sb, const OutView& out, const Scratch& scr,
+                           const MergeLogView& lg, const Work& wk, uint32_t* parts, uint32_t block_grid,
+                           hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
                          uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
@@ -1393,6 +1396,80 @@ int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, co
     if (!a || !out_ba || !log_ba) return CRDT_E_INVALID;
     return delta_pair_log_common(ctx, a->state, a->tombs, a->doc_actor, a->actor, b, out_ab, out_ba, kind_ab,
                                  kind_ba, log_ab, log_ba, stream);
+}
+
+// Logged fold (fold_log.hip).  Workspace: the fold's worklist and scratch copy of
+// the output slots, and the logged join's summary partial sums.  The argument
+// errors are the fold's and the logged join's together.
+int crdt_awset_fold_log_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
+                              const crdt_awset_out* out, const crdt_merge_log* log, void* stream) {
+    if (!ctx || !batch_ptrs_ok(dst) || !src_ptrs_ok(srcs) || !out_ptrs_ok(out)) return CRDT_E_INVALID;
+    if (mode != CRDT_FOLD_AWSET && mode != CRDT_FOLD_DELTA) return CRDT_E_INVALID;
+    if (dst->n_docs != srcs->n_docs || dst->R != srcs->R) return CRDT_E_INVALID;
+    const crdt_merge_log* l = log;
+    if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
+        !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
+        return CRDT_E_INVALID;
+    // No two written arrays start at one address, the per-document arrays, whose
+    // sizes the host knows, do not overlap at all, and no written array starts
+    // where an input array of the same kind starts.
+    const size_t n = dst->n_docs, R = dst->R;
+    struct Range {
+        uintptr_t p;
+        size_t bytes;  // 0: size unknown here (entry arrays)
+        int width;     // bytes per element: the array's kind
+    };
+    std::vector<Range> r = {{(uintptr_t)out->offsets, (n + 1) * 4, 4}, {(uintptr_t)out->counts, n * 4, 4},
+                            {(uintptr_t)out->vv, n * R * 8, 8},       {(uintptr_t)out->keys, 0, 8},
+                            {(uintptr_t)out->actors, 0, 4},           {(uintptr_t)out->counters, 0, 8},
+                            {(uintptr_t)l->flags, n, 1},              {(uintptr_t)l->rem_offsets, (n + 1) * 4, 4},
+                            {(uintptr_t)l->rem_counts, n * 4, 4},     {(uintptr_t)l->ups_offsets, (n + 1) * 4, 4},
+                            {(uintptr_t)l->ups_counts, n * 4, 4},     {(uintptr_t)l->rem_keys, 0, 8},
+                            {(uintptr_t)l->rem_actors, 0, 4},         {(uintptr_t)l->rem_counters, 0, 8},
+                            {(uintptr_t)l->ups_keys, 0, 8},           {(uintptr_t)l->ups_actors, 0, 4},
+                            {(uintptr_t)l->ups_counters, 0, 8}};
+    if (l->summary) r.push_back({(uintptr_t)l->summary, 5 * 4, 4});
+    if (l->ups_kind) r.push_back({(uintptr_t)l->ups_kind, 0, 1});
+    for (size_t i = 0; i < r.size(); ++i)
+        for (size_t j = i + 1; j < r.size(); ++j) {
+            if (r[i].p == r[j].p) return CRDT_E_INVALID;
+            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
+                return CRDT_E_INVALID;
+        }
+    const void* const in4[] = {dst->offsets, dst->counts, dst->actors, srcs->doc_srcs, srcs->src_actor,
+                               srcs->entry_off, srcs->actors, srcs->tomb_off, srcs->tactors};
+    const void* const in8[] = {dst->keys, dst->counters, dst->vv, srcs->vv, srcs->keys, srcs->counters, srcs->tkeys,
+                               srcs->tcounters};
+    for (const Range& w : r) {
+        if (w.width == 4)
+            for (const void* q : in4)
+                if (q && w.p == (uintptr_t)q) return CRDT_E_INVALID;
+        if (w.width == 8)
+            for (const void* q : in8)
+                if (q && w.p == (uintptr_t)q) return CRDT_E_INVALID;
+    }
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(dst->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (rc != CRDT_OK) return rc;
+    if (ctx->scratch_slots == 0) {
+        if (cap) return CRDT_E_WORKSPACE;
+        if (reserve_scratch(ctx, 1) != CRDT_OK) return CRDT_E_NOMEM;
+    }
+    if (dst->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
+    const size_t slots = ctx->scratch_slots;
+    Scratch scr{ctx->scratch.as<uint64_t>(0), ctx->scratch.as<uint32_t>(slots * 16), ctx->scratch.as<uint64_t>(slots * 8),
+                slots};
+    const MergeLogView lv{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
+                          l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
+                          l->ups_actors, l->ups_counters, l->ups_kind};
+    rc = hip_err(launch_fold_log(mode, view(dst), view(srcs), view(out), scr, lv, make_work(ctx),
+                                 ctx->parts.as<uint32_t>(), block_grid(ctx), s));
+    return leave(ctx, s, cap, rc);
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,

@@ -15,8 +15,9 @@
 //    (below), not per step, and the next document's loads are in flight while
 //    the current one is folded.
 //  * fold_block_kernel: every other document (worklist); persistent
-//    workgroups, merge-path walk per step (merge_block.hpp), ping-pong
-//    between the output slots and a scratch copy.
+//    workgroups, merge-path walk per step, ping-pong between the output slots
+//    and a scratch copy (fold_block_doc, merge_block.hpp: the logged fold,
+//    fold_log.hip, runs the same step loop).
 #include "crdt_device.hpp"
 #include "merge_block.hpp"
 #include "wave_sort.hpp"
@@ -1581,65 +1582,9 @@ __global__ __launch_bounds__(NT) void fold_block_kernel(int mode, BatchView dst,
                                                         Work wk) {
     __shared__ MergeSmem<NT, IPT> sm;
     const uint32_t tid = threadIdx.x;
-    const uint32_t R = dst.R;
     uint32_t err = 0;
-    for_each_work(wk, 0u, dst.n_docs, &sm.word[0], [&](uint32_t d) {
-        const uint32_t s0 = sb.doc_srcs[d], s1 = sb.doc_srcs[d + 1];
-        const uint32_t doff = dst.offsets[d];
-        const uint32_t dslots = dst.offsets[d + 1] - doff;
-        const uint32_t obase = doff + sb.entry_off[s0];
-        const uint64_t cap = (uint64_t)dslots + (sb.entry_off[s1] - sb.entry_off[s0]);
-        if ((uint64_t)obase + cap > scr.slots) {  // crdt_ctx_reserve was not told enough slots
-            if (tid == 0) atomicOr(wk.status, kErrWorkspace);
-            __syncthreads();
-            return;
-        }
-        const EntriesOut O{out.keys + obase, out.actors + obase, out.counters + obase};
-        const EntriesOut X{scr.keys + obase, scr.actors + obase, scr.counters + obase};
-        const uint32_t live = live_count(dst.offsets, dst.counts, d);
-        if (live > dslots && tid == 0) atomicOr(wk.status, kErrCapacity);
-        Entries cur{dst.keys + doff, dst.actors + doff, dst.counters + doff, live < dslots ? live : dslots};
-        int where = 0;  // 0 = input, 1 = out, 2 = scratch
-        if (tid < R) sm.dvv[tid] = dst.vv[(size_t)d * R + tid];
-        __syncthreads();
-        bool stop = false;
-        for (uint32_t k = s0; k < s1 && !stop; ++k) {
-            const uint32_t e0 = sb.entry_off[k];
-            const Entries S{sb.keys + e0, sb.actors + e0, sb.counters + e0, sb.entry_off[k + 1] - e0};
-            Entries Tm{nullptr, nullptr, nullptr, 0};
-            if (sb.tomb_off && mode == CRDT_FOLD_DELTA) {
-                const uint32_t t0 = sb.tomb_off[k];
-                Tm = Entries{sb.tkeys + t0, sb.tactors + t0, sb.tcounters + t0, sb.tomb_off[k + 1] - t0};
-            }
-            if (tid < R) sm.svv[tid] = sb.vv[(size_t)k * R + tid];
-            __syncthreads();
-            uint32_t perr = 0;
-            const bool full = (mode != CRDT_FOLD_DELTA) || vv_counter(sm.dvv, R, sb.src_actor[k], perr) == 0;
-            if (perr) {
-                err |= perr;
-                stop = true;
-                break;
-            }
-            if (!full && !delta_changes<NT>(S, Tm, sm.dvv, R, err)) continue;
-            const EntriesOut& tgt = (where == 1) ? X : O;
-            const uint32_t n = block_merge<NT, IPT>(cur, S, full ? Entries{nullptr, nullptr, nullptr, 0} : Tm, full, R,
-                                                    sm, tgt, err);
-            if (tid < R) sm.dvv[tid] = max(sm.dvv[tid], sm.svv[tid]);
-            where = (where == 1) ? 2 : 1;
-            cur = Entries{tgt.k, tgt.a, tgt.c, n};
-            __syncthreads();
-        }
-        if (where != 1) {  // result still in the input or the scratch copy
-            for (uint32_t i = tid; i < cur.n; i += NT) {
-                O.k[i] = cur.k[i];
-                O.a[i] = cur.a[i];
-                O.c[i] = cur.c[i];
-            }
-        }
-        if (tid == 0) out.counts[d] = cur.n;
-        if (tid < R) out.vv[(size_t)d * R + tid] = sm.dvv[tid];
-        __syncthreads();
-    });
+    for_each_work(wk, 0u, dst.n_docs, &sm.word[0],
+                  [&](uint32_t d) { fold_block_doc<NT, IPT>(mode, dst, sb, out, scr, wk, d, sm, err); });
     if (__syncthreads_or(err != 0) && tid == 0) atomicOr(wk.status, kErrActorRange);
 }
 

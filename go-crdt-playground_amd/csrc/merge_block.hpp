@@ -10,8 +10,9 @@
 // block_merge places the survivors (KeepSink: join.hip, fold.hip, delta_pair.hip);
 // the logged merges add the removed and upserted records beside them (LogSink,
 // merge_log.hpp: join_log.hip, delta_pair_log.hip).  The file also holds what the block kernels share around
-// the walk: the worklist loop (for_each_work) and the test whether a delta source
-// changes anything (delta_changes).
+// the walk: the worklist loop (for_each_work), the test whether a delta source
+// changes anything (delta_changes) and the ordered fold of one worklist document
+// (fold_block_doc: fold.hip, fold_log.hip).
 //
 // The rule (union key k, dst dot d if present, src dot s if present):
 //   changed  = has_s && (full || !dstVV.HasDot(s))   awset-delta_test.go:84-92
@@ -181,10 +182,15 @@ struct KeepSink {
 // straddles a window boundary is kept, UPDATED or dropped exactly once; the src
 // entry is skipped in the next window by prev_dk.
 //
+// DIFF: the same walk as a comparison of two states, D the one before and S the
+// one after (diff_walk, merge_log.hpp): no rule and no clock is asked.  A common
+// key is kept with S's dot (UPDATED when it differs from D's), a D-only key is
+// dropped and an S-only key kept.
+//
 // (Not __forceinline__, like block_merge: inlined early, the walk costs the keep /
 // drop kernels 20 to 30 VGPRs; the callers that pop the worklist are forced
 // instead, so that no kernel ends up with a call.)
-template <int NT, int IPT, class Sink>
+template <int NT, int IPT, class Sink, bool DIFF = false>
 __device__ void merge_walk(const Entries& D, const Entries& S, const Entries& tomb, bool full,
                                            uint32_t R, MergeSmem<NT, IPT>& sm, Sink& sink, uint32_t& err) {
     constexpr uint32_t T = NT * IPT;
@@ -229,8 +235,15 @@ __device__ void merge_walk(const Entries& D, const Entries& S, const Entries& to
                     const bool match = (b < ns) && sm.sk[b] == key;
                     const uint32_t d_a = sm.da[a], s_a = match ? sm.sa[b] : 0u;
                     const uint64_t d_c = sm.dc[a], s_c = match ? sm.sc[b] : 0ull;
-                    const bool kp = decide(true, d_a, d_c, match, s_a, s_c, full, sm.dvv, sm.svv, R, tomb, key, oa[q],
-                                           oc[q], err);
+                    bool kp;
+                    if constexpr (DIFF) {
+                        kp = match;
+                        oa[q] = s_a;
+                        oc[q] = s_c;
+                    } else {
+                        kp = decide(true, d_a, d_c, match, s_a, s_c, full, sm.dvv, sm.svv, R, tomb, key, oa[q], oc[q],
+                                    err);
+                    }
                     ok[q] = key;
                     cls[q] = kp ? kPosKeep : kPosRem;
                     if (Sink::kLog) {
@@ -248,8 +261,15 @@ __device__ void merge_walk(const Entries& D, const Entries& S, const Entries& to
                     const uint64_t key = sm.sk[b];
                     const bool match = (a > 0) ? (sm.dk[a - 1] == key) : (has_prev && prev_dk == key);
                     if (!match) {
-                        const bool kp = decide(false, 0u, 0ull, true, sm.sa[b], sm.sc[b], full, sm.dvv, sm.svv, R, tomb,
-                                               key, oa[q], oc[q], err);
+                        bool kp;
+                        if constexpr (DIFF) {
+                            kp = true;
+                            oa[q] = sm.sa[b];
+                            oc[q] = sm.sc[b];
+                        } else {
+                            kp = decide(false, 0u, 0ull, true, sm.sa[b], sm.sc[b], full, sm.dvv, sm.svv, R, tomb, key,
+                                        oa[q], oc[q], err);
+                        }
                         ok[q] = key;
                         cls[q] = kp ? (kPosKeep | kPosAdd) : 0;
                     }
@@ -290,6 +310,80 @@ __device__ __forceinline__ bool delta_changes(const Entries& S, const Entries& T
         any |= !readded;
     }
     return __syncthreads_or(any) != 0;
+}
+
+// The ordered fold of one worklist document by the whole workgroup (fold.hip,
+// fold_log.hip): every source of d merged into it in turn, one window walk per
+// step, ping-ponging between the output slots and the context's scratch copy
+// of them, so that out holds the result once the last step is done.  Returns
+// the live entries written to out (and leaves the merged clock in sm.dvv), or
+// kFoldNoDoc when the scratch is too small for the document (kErrWorkspace:
+// nothing of d is written).  An actor-range error is left in err; the other
+// reports go to wk.status directly.
+constexpr uint32_t kFoldNoDoc = 0xFFFFFFFFu;
+
+template <int NT, int IPT>
+__device__ __forceinline__ uint32_t fold_block_doc(int mode, const BatchView& dst, const SrcView& sb,
+                                                   const OutView& out, const Scratch& scr, const Work& wk,
+                                                   uint32_t d, MergeSmem<NT, IPT>& sm, uint32_t& err) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t R = dst.R;
+    const uint32_t s0 = sb.doc_srcs[d], s1 = sb.doc_srcs[d + 1];
+    const uint32_t doff = dst.offsets[d];
+    const uint32_t dslots = dst.offsets[d + 1] - doff;
+    const uint32_t obase = doff + sb.entry_off[s0];
+    const uint64_t cap = (uint64_t)dslots + (sb.entry_off[s1] - sb.entry_off[s0]);
+    if ((uint64_t)obase + cap > scr.slots) {  // crdt_ctx_reserve was not told enough slots
+        if (tid == 0) atomicOr(wk.status, kErrWorkspace);
+        __syncthreads();
+        return kFoldNoDoc;
+    }
+    const EntriesOut O{out.keys + obase, out.actors + obase, out.counters + obase};
+    const EntriesOut X{scr.keys + obase, scr.actors + obase, scr.counters + obase};
+    const uint32_t live = live_count(dst.offsets, dst.counts, d);
+    if (live > dslots && tid == 0) atomicOr(wk.status, kErrCapacity);
+    Entries cur{dst.keys + doff, dst.actors + doff, dst.counters + doff, live < dslots ? live : dslots};
+    int where = 0;  // 0 = input, 1 = out, 2 = scratch
+    if (tid < R) sm.dvv[tid] = dst.vv[(size_t)d * R + tid];
+    __syncthreads();
+    bool stop = false;
+    for (uint32_t k = s0; k < s1 && !stop; ++k) {
+        const uint32_t e0 = sb.entry_off[k];
+        const Entries S{sb.keys + e0, sb.actors + e0, sb.counters + e0, sb.entry_off[k + 1] - e0};
+        Entries Tm{nullptr, nullptr, nullptr, 0};
+        if (sb.tomb_off && mode == CRDT_FOLD_DELTA) {
+            const uint32_t t0 = sb.tomb_off[k];
+            Tm = Entries{sb.tkeys + t0, sb.tactors + t0, sb.tcounters + t0, sb.tomb_off[k + 1] - t0};
+        }
+        if (tid < R) sm.svv[tid] = sb.vv[(size_t)k * R + tid];
+        __syncthreads();
+        uint32_t perr = 0;
+        const bool full = (mode != CRDT_FOLD_DELTA) || vv_counter(sm.dvv, R, sb.src_actor[k], perr) == 0;
+        if (perr) {
+            err |= perr;
+            stop = true;
+            break;
+        }
+        if (!full && !delta_changes<NT>(S, Tm, sm.dvv, R, err)) continue;
+        const EntriesOut& tgt = (where == 1) ? X : O;
+        const uint32_t n = block_merge<NT, IPT>(cur, S, full ? Entries{nullptr, nullptr, nullptr, 0} : Tm, full, R, sm,
+                                                tgt, err);
+        if (tid < R) sm.dvv[tid] = max(sm.dvv[tid], sm.svv[tid]);
+        where = (where == 1) ? 2 : 1;
+        cur = Entries{tgt.k, tgt.a, tgt.c, n};
+        __syncthreads();
+    }
+    if (where != 1) {  // result still in the input or the scratch copy
+        for (uint32_t i = tid; i < cur.n; i += NT) {
+            O.k[i] = cur.k[i];
+            O.a[i] = cur.a[i];
+            O.c[i] = cur.c[i];
+        }
+    }
+    if (tid == 0) out.counts[d] = cur.n;
+    if (tid < R) out.vv[(size_t)d * R + tid] = sm.dvv[tid];
+    __syncthreads();
+    return cur.n;
 }
 
 // The block path's worklist: workgroups pop documents from head word `head` of

@@ -1,9 +1,10 @@
-// The decision log of a pair merge (join_log.hip, delta_pair_log.hip): what the
-// logged kernels share beyond the merge itself.  The per-direction summary sums
+// The decision log of a merge (join_log.hip, delta_pair_log.hip, fold_log.hip): what
+// the logged kernels share beyond the merge itself.  The per-direction summary sums
 // (LogSums: added up per wave or workgroup, flushed with integer atomics into
 // kLogParts spread rows of the context's partials buffer, reduced by
 // join_log_summary_kernel), the flag byte of a document, and the window walk's
-// logging sink (LogSink; merge_block.hpp, merge_walk).  The zero and summary
+// logging sink (LogSink; merge_block.hpp, merge_walk) with its sibling for the
+// comparison of two states (DiffSink, diff_walk).  The zero and summary
 // kernels live in join_log.hip and are launched through the two functions
 // declared at the end.
 #pragma once
@@ -85,6 +86,54 @@ struct LogSink {
         o_ups += total_ups;
     }
 };
+
+// LogSink's sibling for a walk that compares two states (the logged fold's block
+// path, fold_log.hip): the state after is in place already, so only the two lists
+// are written, with two running offsets.
+struct DiffSink {
+    static constexpr bool kLog = true;
+    EntriesOut rem, ups;
+    uint8_t* ups_kind;      // NULL: none
+    uint32_t o_rem, o_ups;  // written so far: removed (<= the entries before), upserted (<= the entries after)
+    uint32_t my_upd;        // UPDATED records this thread has written
+
+    template <int NT, int IPT>
+    __device__ __forceinline__ void place(const uint8_t (&cls)[IPT], const uint64_t (&ok)[IPT],
+                                          const uint32_t (&oa)[IPT], const uint64_t (&oc)[IPT], uint32_t* wave_tot) {
+        uint32_t cnt_rem = 0, cnt_ups = 0;
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            cnt_rem += (cls[q] & kPosRem) ? 1u : 0u;
+            cnt_ups += (cls[q] & (kPosAdd | kPosUpd)) ? 1u : 0u;
+            my_upd += (cls[q] & kPosUpd) ? 1u : 0u;
+        }
+        uint32_t total_rem, total_ups;
+        uint32_t pos_rem = o_rem + block_exclusive_scan<NT>(cnt_rem, wave_tot, &total_rem);
+        uint32_t pos_ups = o_ups + block_exclusive_scan<NT>(cnt_ups, wave_tot, &total_ups);
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            if (cls[q] & kPosRem) put_entry(rem, pos_rem++, ok[q], oa[q], oc[q]);
+            if (cls[q] & (kPosAdd | kPosUpd)) {
+                put_entry(ups, pos_ups, ok[q], oa[q], oc[q]);
+                if (ups_kind) ups_kind[pos_ups] = (uint8_t)((cls[q] & kPosUpd) ? CRDT_DIFF_UPDATED : CRDT_DIFF_ADDED);
+                ++pos_ups;
+            }
+        }
+        o_rem += total_rem;
+        o_ups += total_ups;
+    }
+};
+
+// The window walk as a comparison (merge_block.hpp, merge_walk<.., DIFF>): the
+// entries of `before` whose key `after` lacks are handed to the sink as removed
+// with their own dot, the entries of `after` whose key `before` lacks as added
+// and those it holds under another dot as updated, each with after's dot.
+template <int NT, int IPT, class Sink>
+__device__ __forceinline__ void diff_walk(const Entries& before, const Entries& after, MergeSmem<NT, IPT>& sm,
+                                          Sink& sink) {
+    uint32_t unused = 0;
+    merge_walk<NT, IPT, Sink, true>(before, after, Entries{nullptr, nullptr, nullptr, 0u}, true, 0u, sm, sink, unused);
+}
 
 // Bytes of the partials buffer both directions' rows take.
 size_t join_log_parts_bytes();

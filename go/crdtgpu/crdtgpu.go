@@ -812,6 +812,26 @@ func (e *Engine) ExchangeLog(a, b *C.crdt_awset_batch, outAB, outBA *C.crdt_awse
 	return nil
 }
 
+// FoldLog is crdt_awset_fold_async with the log of the whole ordered fold written
+// beside the merged state (crdt_awset_fold_log_async): out holds what the fold
+// writes; log's removed list of document d starts at dst.offsets[d], its upserted
+// list at entry_off[doc_srcs[d]] with the document's source entry slots for
+// capacity. The log is the fold's net effect, crdt_awset_diff_async(dst, out)'s
+// answer: steps in between do not show. mode is C.CRDT_FOLD_AWSET or
+// C.CRDT_FOLD_DELTA; the receiver of a delta message gets its index updates from
+// this call. Asynchronous on stream; device-side errors surface at the context's
+// next sync.
+func (e *Engine) FoldLog(mode int, dst *C.crdt_awset_batch, srcs *C.crdt_src_batch, out *C.crdt_awset_out,
+	log *MergeLog, stream unsafe.Pointer) error {
+	if dst == nil || srcs == nil || out == nil || log == nil {
+		return fmt.Errorf("FoldLog: nil argument")
+	}
+	if rc := C.crdt_awset_fold_log_async(e.ctx, C.int(mode), dst, srcs, out, &log.Log, stream); rc != 0 {
+		return errOf("crdt_awset_fold_log_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- delta merge of a resident pair
 
 // DeltaJoin is (*AWSetDelta).Merge on resident replicas as they stand

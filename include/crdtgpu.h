@@ -51,6 +51,9 @@
  *   crdt_awset_join_log_async / crdt_awset_exchange_log_async
  *       the join and the exchange with that log written beside the merged
  *       state, from the one read the merge needs   awset.go:103-161
+ *   crdt_awset_fold_log_async
+ *       the fold, in either mode, with the log of its net effect: what the
+ *       receiver of a delta message and an N-way merge report to an index
  *   crdt_awset_sources_async
  *       P resident replicas of every document gathered into the packed source
  *       batch the folds and the delta extraction read (no reference
@@ -1035,6 +1038,62 @@ int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, co
                                         const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
                                         uint8_t* kind_ab, uint8_t* kind_ba /* each [n_docs] or NULL */,
                                         const crdt_merge_log* log_ab, const crdt_merge_log* log_ba, void* stream);
+
+/* ---- logged fold: the ordered fold with the log of its net effect --------------
+ * The pair-form logged calls above need both replicas resident on one device.
+ * The receiver of a delta message (crdt_awset_delta_extract_* packs one as a
+ * crdt_src_batch) and an N-way convergence merge their sources with the fold;
+ * this call is crdt_awset_fold_async with the log beside the merged state.
+ * The merged state: out holds what crdt_awset_fold_async(mode, dst, srcs, out)
+ * writes for the same inputs -- live entries, counts, offsets and clocks bit for
+ * bit, document d at dst.offsets[d] + entry_off[doc_srcs[d]], slack unspecified.
+ * The log is the net effect of the whole ordered fold: exactly
+ * crdt_awset_diff_async(before = dst, after = out)'s answer, per document d.
+ *   - removed: the live entries of dst[d] whose key is not live in out[d], in
+ *     key order, with the dot they had in dst.
+ *   - upserted: the live entries of out[d] whose key was not live in dst[d]
+ *     (CRDT_DIFF_ADDED) or was live there under a different (actor, counter)
+ *     (CRDT_DIFF_UPDATED), in key order, with their final dot.
+ *   - flags[d] and summary as the diff writes them; CRDT_DIFF_CLOCK iff dst.vv
+ *     and out.vv differ in some r < R.
+ * Intermediate steps do not show: a key that one step removes and a later step
+ * adds again under the same dot leaves no record (under another dot: one
+ * UPDATED); a key added and later removed leaves none; a key updated and later
+ * removed leaves one removed record, with dst's dot.
+ * Layout: no scan over documents.  The removed list of d starts at
+ * dst.offsets[d]; rem_offsets repeats dst.offsets (n_docs + 1 values) and its
+ * capacity is dst's slots.  The upserted list of d starts at
+ * entry_off[doc_srcs[d]]: ups_offsets[d] = entry_off[doc_srcs[d]] for d <= n_docs,
+ * and its capacity is the sources' entry slots of the document.  That is enough:
+ * an upserted key ends under a dot dst did not hold for it, a step gives a key
+ * no other dot than the one its source's entry of that key carries, so every
+ * upserted key is the key of some source entry of d, and distinct keys need
+ * distinct entries.  ups_kind is indexed like ups_keys.  Each list read as
+ * (offsets, counts, keys, actors, counters) is a valid crdt_tomb_batch.  Slots
+ * of a document at or past its count are unspecified; slots of other documents
+ * are never written.  No atomic decides a position: the bits are the same on
+ * every run.
+ * srcs->tomb_off == NULL: no tombstones.  CRDT_FOLD_AWSET ignores tombstones.
+ * Reported by crdt_ctx_sync, exactly as the fold reports them:
+ *   CRDT_E_ACTOR_RANGE  where Go evaluates HasDot / Counter at actor == R
+ *   CRDT_E_CAPACITY     a live count above its slots (clamped)
+ *   CRDT_E_WORKSPACE    a document too large for one wavefront (more than 64
+ *                       entries in dst, in a source, in a source's tombstones or
+ *                       after some step) needs more fold slots than
+ *                       crdt_ctx_reserve was given, or a workspace would have to
+ *                       grow during a graph capture
+ * Returned by the call (CRDT_E_INVALID): a NULL argument or a NULL required field
+ * (summary and ups_kind may be NULL); an n_docs or R mismatch; R out of range; a
+ * bad mode; two written arrays starting at one address or overlapping
+ * per-document arrays; a written array starting where an input array of the same
+ * kind starts.
+ * n_docs == 0 launches nothing that reads documents; summary, when given, is
+ * zeroed.  Ordered after the context's previous call; no host sync, kernel nodes
+ * only, capturable.  Workspace: the fold's (worklist and fold slots, sized by
+ * crdt_ctx_reserve) and the logged join's fixed 64 KB of summary partial sums.
+ * There is no _batch form. */
+int crdt_awset_fold_log_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
+                              const crdt_awset_out* out, const crdt_merge_log* log, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
