@@ -306,8 +306,10 @@ __device__ __forceinline__ uint32_t slab_chunk(const SlabMap& m, uint32_t c) {
 }
 
 // The count as the producer wrote it, unclamped: for the callers that compare it
-// with the slots themselves (fold_block_kernel), only size work by it (the tile
-// geometry), or take it as given (join_block_kernel, apply.hip).
+// with the slots themselves (fold_block_kernel) or take it as given (apply.hip's
+// tombstone GC).  The join does neither: its wave kernel clamps in vector form
+// (join.hip, meta_vec_issue), join_block_kernel with live_span, and the tile plan,
+// geometry and split with live_clamped below.
 __device__ __forceinline__ uint32_t live_count(const uint32_t* offsets, const uint32_t* counts, uint32_t d) {
     return counts ? counts[d] : offsets[d + 1] - offsets[d];
 }
@@ -323,6 +325,13 @@ __device__ __forceinline__ uint32_t live_span(const uint32_t* off, const uint32_
     if (live > slots) err |= kErrCapacity;
     o = b;
     return min(live, slots);
+}
+
+// live_span's length alone, for the callers that must agree on it among
+// themselves and leave the report to one of them (tile.hip).
+__device__ __forceinline__ uint32_t live_clamped(const uint32_t* off, const uint32_t* cnt, uint32_t d) {
+    uint32_t o, e = 0;
+    return live_span(off, cnt, d, o, e);
 }
 
 // VersionVector.HasDot (crdt-misc.go:28-34) against a VV of length R held in

@@ -49,41 +49,41 @@ struct JoinMeta {
 // seven workgroups after it -- which run on the other XCDs, so each XCD's L2
 // would pull nearly every metadata line of the batch.
 struct MetaVec {
-    uint32_t doff, soff, dend, send, dnx, snx;
+    uint32_t doff, soff, dn, sn, cap;
 };
 
+// Lane i's live counts are clamped to its document's slots here, once, in vector
+// form (one lane is one document; live_span's rule, kErrCapacity into err for the
+// wave's own documents): everything downstream -- the large ballot, the buffer
+// descriptors of the entry loads, the capacity of the padded stores, and through
+// the worklist the block and tile paths' choice -- sees the clamped sizes.  The
+// next document's slot bound is loaded for that whatever CRDT_JOIN_PAD_STORES is.
 __device__ __forceinline__ MetaVec meta_vec_issue(const BatchView& dst, const BatchView& src, uint32_t first,
-                                                  uint32_t stride, uint32_t cnt, uint32_t lane) {
+                                                  uint32_t stride, uint32_t cnt, uint32_t lane, uint32_t& err) {
     const uint32_t n = dst.n_docs;
     const uint32_t d0 = lane < cnt ? first + lane * stride : first;
     const uint32_t dd = d0 < n ? d0 : n - 1;
     MetaVec v;
     v.doff = dst.offsets[dd];
     v.soff = src.offsets[dd];
-    v.dend = dst.counts ? dst.counts[dd] : dst.offsets[dd + 1];
-    v.send = src.counts ? src.counts[dd] : src.offsets[dd + 1];
-    if (CRDT_JOIN_PAD_STORES) {  // slot bounds of the next document: the output capacity
-        v.dnx = dst.counts ? dst.offsets[dd + 1] : v.dend;
-        v.snx = src.counts ? src.offsets[dd + 1] : v.send;
-    } else {
-        v.dnx = v.snx = 0;
-    }
+    const uint32_t dnx = dst.offsets[dd + 1], snx = src.offsets[dd + 1];
+    const uint32_t dslots = dnx > v.doff ? dnx - v.doff : 0u, sslots = snx > v.soff ? snx - v.soff : 0u;
+    const uint32_t dlive = dst.counts ? dst.counts[dd] : dslots;
+    const uint32_t slive = src.counts ? src.counts[dd] : sslots;
+    err |= (lane < cnt && (dlive > dslots || slive > sslots)) ? kErrCapacity : 0u;
+    v.dn = min(dlive, dslots);
+    v.sn = min(slive, sslots);
+    v.cap = dslots + sslots;  // the document's output capacity (the padded stores stay within it)
     return v;
 }
 
-__device__ __forceinline__ JoinMeta meta_of(const BatchView& dst, const BatchView& src, const MetaVec& v,
-                                            uint32_t i) {
+__device__ __forceinline__ JoinMeta meta_of(const MetaVec& v, uint32_t i) {
     JoinMeta m;
     m.doff = (uint32_t)__builtin_amdgcn_readlane((int)v.doff, (int)i);
     m.soff = (uint32_t)__builtin_amdgcn_readlane((int)v.soff, (int)i);
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v.dend, (int)i);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v.send, (int)i);
-    m.dn = dst.counts ? a : a - m.doff;
-    m.sn = src.counts ? b : b - m.soff;
-    m.cap = 0;
-    if (CRDT_JOIN_PAD_STORES)
-        m.cap = (uint32_t)__builtin_amdgcn_readlane((int)v.dnx, (int)i) - m.doff +
-                (uint32_t)__builtin_amdgcn_readlane((int)v.snx, (int)i) - m.soff;
+    m.dn = (uint32_t)__builtin_amdgcn_readlane((int)v.dn, (int)i);
+    m.sn = (uint32_t)__builtin_amdgcn_readlane((int)v.sn, (int)i);
+    m.cap = CRDT_JOIN_PAD_STORES ? (uint32_t)__builtin_amdgcn_readlane((int)v.cap, (int)i) : 0u;
     return m;
 }
 
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
     const uint32_t first = uniform(chunk * (WAVES * K) + w);
     if (first >= n_docs) return;
     const uint32_t cnt = min((uint32_t)K, (n_docs - first + WAVES - 1) / WAVES);
-    const MetaVec mv = meta_vec_issue(dst, src, first, WAVES, cnt, lane);
+    const MetaVec mv = meta_vec_issue(dst, src, first, WAVES, cnt, lane, err);
 
     auto push_large = [&](uint32_t dd) {
         if (CRDT_JOIN_WAVE_PUSH) return;  // pushed below, all at once
@@ -328,9 +328,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
         // the worklist with ONE atomic on its counter: config 4 pushes 10,800
         // documents, and one counter word takes ~88 M atomics/s, so a push per
         // document serialised ~0.1 ms of the launch on that word.
-        const uint32_t dn_l = dst.counts ? mv.dend : mv.dend - mv.doff;
-        const uint32_t sn_l = src.counts ? mv.send : mv.send - mv.soff;
-        const bool large = lane < cnt && (dn_l > 64 || sn_l > 64);
+        const bool large = lane < cnt && (mv.dn > 64 || mv.sn > 64);  // (the clamped sizes)
         const uint64_t bl = ballot(large);
         if (bl) {
             if (no_large) {
@@ -350,7 +348,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
         }
     }
 
-    JoinMeta m = meta_of(dst, src, mv, 0);
+    JoinMeta m = meta_of(mv, 0);
     uint32_t d = first;
     bool small = m.dn <= 64 && m.sn <= 64;
     JoinLanes LA, LB;
@@ -359,7 +357,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
     for (uint32_t k = 0;;) {
         // A: issue k+1 into LB, merge LA
         bool more = k + 1 < cnt;
-        JoinMeta mn = meta_of(dst, src, mv, more ? k + 1 : 0);
+        JoinMeta mn = meta_of(mv, more ? k + 1 : 0);
         uint32_t dn = d + WAVES;
         bool small_n = more && mn.dn <= 64 && mn.sn <= 64;
         lanes_issue(LB, dst, src, mn, dn, small_n, lane, R);
@@ -372,7 +370,7 @@ __global__ __launch_bounds__(WAVES * 64) CRDT_JOIN_WPE_ATTR void join_wave_kerne
         small = small_n;
         // B: issue k+1 into LA, merge LB
         more = k + 1 < cnt;
-        mn = meta_of(dst, src, mv, more ? k + 1 : 0);
+        mn = meta_of(mv, more ? k + 1 : 0);
         dn = d + WAVES;
         small_n = more && mn.dn <= 64 && mn.sn <= 64;
         lanes_issue(LA, dst, src, mn, dn, small_n, lane, R);
@@ -400,9 +398,12 @@ __global__ __launch_bounds__(NT) void join_block_kernel(BatchView dst, BatchView
     uint32_t err = 0;
     const Entries none{nullptr, nullptr, nullptr, 0};
     for_each_work(wk, head, dst.n_docs, &sm.word[0], [&](uint32_t d) {
-        const uint32_t doff = dst.offsets[d], soff = src.offsets[d];
-        const Entries D{dst.keys + doff, dst.actors + doff, dst.counters + doff, live_count(dst.offsets, dst.counts, d)};
-        const Entries S{src.keys + soff, src.actors + soff, src.counters + soff, live_count(src.offsets, src.counts, d)};
+        uint32_t doff, soff, cerr = 0;  // live prefixes clamped to the slots (kErrCapacity)
+        const uint32_t dn = live_span(dst.offsets, dst.counts, d, doff, cerr);
+        const uint32_t sn = live_span(src.offsets, src.counts, d, soff, cerr);
+        if (cerr && tid == 0) atomicOr(wk.status, kErrCapacity);
+        const Entries D{dst.keys + doff, dst.actors + doff, dst.counters + doff, dn};
+        const Entries S{src.keys + soff, src.actors + soff, src.counters + soff, sn};
         if (tid < R) {
             sm.dvv[tid] = dst.vv[(size_t)d * R + tid];
             sm.svv[tid] = src.vv[(size_t)d * R + tid];

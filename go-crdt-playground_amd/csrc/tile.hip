@@ -59,9 +59,16 @@ __global__ __launch_bounds__(NT) void tile_count_kernel(BatchView A, BatchView B
             uint32_t n = 0;
             if (slot < total_slots && slot < (r + 1) * kRun) {
                 const uint32_t d = wk.worklist[slot];
-                n = d < A.n_docs ? doc_tiles(live_count(A.offsets, A.counts, d), live_count(B.offsets, B.counts, d),
-                                             tw.tile)
-                                 : 1u;
+                n = 1u;
+                if (d < A.n_docs) {
+                    // live counts clamped to the slots: the plan here, the split and the geometry
+                    // (live_clamped) size a document alike; this one, once per slot, reports
+                    uint32_t o, err = 0;
+                    const uint32_t nd = live_span(A.offsets, A.counts, d, o, err);
+                    const uint32_t ns = live_span(B.offsets, B.counts, d, o, err);
+                    if (err) atomicOr(wk.status, kErrCapacity);
+                    n = doc_tiles(nd, ns, tw.tile);
+                }
             }
             uint32_t tot;
             const uint32_t ex = block_exclusive_scan<NT>(n, wave_tot, &tot);
@@ -213,7 +220,7 @@ __global__ __launch_bounds__(NT) void tile_split_kernel(BatchView A, BatchView B
         const uint32_t d = wk.worklist[slot];
         uint32_t i0 = 0, j0 = 0;
         if (d < A.n_docs) {
-            const uint32_t nd = live_count(A.offsets, A.counts, d), ns = live_count(B.offsets, B.counts, d);
+            const uint32_t nd = live_clamped(A.offsets, A.counts, d), ns = live_clamped(B.offsets, B.counts, d);
             const uint32_t k0 = min(t * tw.tile, nd + ns);
             uint32_t lo = k0 > ns ? k0 - ns : 0u, hi = k0 < nd ? k0 : nd;
             const uint64_t* dk = A.keys + A.offsets[d];
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(256) void tile_geo_kernel(BatchView A, BatchView B,
         const uint32_t d = ds.x, t = ds.y, i0 = ds.z, j0 = ds.w;
         uint4 r0 = make_uint4(d, t, 0u, 0u), r1 = make_uint4(0u, 0u, kGeoLast, 0u);
         if (d < A.n_docs) {
-            const uint32_t nd = live_count(A.offsets, A.counts, d), ns = live_count(B.offsets, B.counts, d);
+            const uint32_t nd = live_clamped(A.offsets, A.counts, d), ns = live_clamped(B.offsets, B.counts, d);
             const uint32_t aoff = A.offsets[d], boff = B.offsets[d];
             uint32_t i1 = nd, j1 = ns, last = kGeoLast;
             if (ps.base + l + 1 < total) {  // (desc[count] is the next pass's first tile)

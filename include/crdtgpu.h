@@ -241,7 +241,11 @@ int crdt_ctx_sync(crdt_ctx* ctx, void* stream);
 const char* crdt_strerror(int code);
 int crdt_abi_version(void);
 
-/* ---- device-resident, asynchronous on a HIP stream (NULL = default) ---- */
+/* ---- device-resident, asynchronous on a HIP stream (NULL = default) ----
+ * Join and exchange: a live count above a document's slots is clamped to them
+ * and crdt_ctx_sync returns CRDT_E_CAPACITY; the document is then the join of
+ * the clamped prefixes, every other document is what it would be without the
+ * bad count, and no slot of another document is read as live or written. */
 int crdt_awset_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_awset_batch* src,
                           const crdt_awset_out* out, void* stream);
 /* Anti-entropy exchange: out_ab[d] = a[d] <- b[d] AND out_ba[d] = b[d] <- a[d]
