@@ -259,6 +259,8 @@ def signatures():
         "crdt_validate_tomb_batch": (ctypes.c_int, [P(CTombBatch), _u32]),
         "crdt_awset_apply_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), P(COpBatch), P(CAWSetOut),
                                                   P(CTombOut), _vp]),
+        "crdt_awset_apply_log_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), P(COpBatch), P(CAWSetOut),
+                                                      P(CTombOut), P(CMergeLog), _vp]),
         "crdt_awset_apply_batch": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), P(COpBatch), P(CAWSetOut),
                                                   P(CTombOut)]),
         "crdt_awset_sort_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _u32, P(CAWSetOut), _vp]),

@@ -248,6 +248,53 @@ class Engine:
             setattr(hl, f, a)
         return h, hl
 
+    def apply_log_async(self, state: AWSetBatch, ops: OpBatch, out: OutBuffers, log: MergeLogBuffers,
+                        tombs: TombBatch = None, tomb_out: TombBuffers = None, stream=None):
+        """apply_async with the log of what the ops changed beside the new state: per doc, the
+        state entries removed (at state.offsets[d], with the dot they had) and the entries an
+        ADD left new or under another dot (at op_off[d], capacity the doc's ops) -- what
+        diff_async(state, out) reports; tombstone changes are not part of it, a refused doc's
+        log is empty (crdt_awset_apply_log_async)."""
+        cs, co, cout, lg = _c(state), _c(ops), _c(out), _c(log)
+        ct = _c(tombs) if tombs is not None else None
+        cto = tomb_out.c_out() if tomb_out is not None else None
+        check(self._lib.crdt_awset_apply_log_async(self._ctx, ctypes.byref(cs), ctypes.byref(ct) if ct else None,
+                                                   ctypes.byref(co), ctypes.byref(cout),
+                                                   ctypes.byref(cto) if cto else None, ctypes.byref(lg),
+                                                   _stream(stream)), "crdt_awset_apply_log_async")
+
+    def apply_log(self, state: AWSetBatch, ops: OpBatch, tombs: TombBatch = None, with_tombs: bool = True):
+        """Host batches uploaded, the ops applied with the log on the device and downloaded:
+        (entries out, tombstones out or None, the log as host MergeLogBuffers), the first two as
+        apply returns them (for tests and small callers)."""
+        import numpy as np
+        import torch
+
+        state, ops = state.numpy(), ops.numpy()
+        tombs = tombs.numpy() if tombs is not None else None
+        n, R = state.n_docs, state.R
+        ss, nops = int(state.offsets[-1]), int(ops.op_off[-1])
+        ts = (int(tombs.offsets[-1]) if tombs is not None else 0) + nops
+        dev = torch.device("cuda", self.device)
+        out = OutBuffers(n, R, ss + nops, device=dev)
+        tout = TombBuffers(n, ts, device=dev) if with_tombs else None
+        log = MergeLogBuffers(n, ss, nops, device=dev)
+        self.apply_log_async(state.to(dev), ops.to(dev), out, log, tombs.to(dev) if tombs is not None else None, tout)
+        self.sync()
+        h = OutBuffers(n, R, ss + nops)
+        h.offsets, h.counts, h.vv = _np(out.offsets, np.uint32), _np(out.counts, np.uint32), _np(out.vv, np.uint64)
+        h.keys, h.actors, h.counters = _np(out.keys, np.uint64), _np(out.actors, np.uint32), _np(out.counters, np.uint64)
+        ht = None
+        if with_tombs:
+            ht = TombBuffers(n, ts)
+            ht.offsets, ht.counts = _np(tout.offsets, np.uint32), _np(tout.counts, np.uint32)
+            ht.keys, ht.actors, ht.counters = (_np(tout.keys, np.uint64), _np(tout.actors, np.uint32),
+                                               _np(tout.counters, np.uint64))
+        hl = MergeLogBuffers(n, ss, nops)
+        for f, a in log.numpy().items():
+            setattr(hl, f, a)
+        return h, ht, hl
+
     def digest_async(self, state: AWSetBatch, out, tombs: TombBatch = None, stream=None):
         """Per doc, the 16-byte digest of its live state into `out` (device u64 [2 * n_docs]):
         word 0 the element set, word 1 elements, dots, Deleted and clock

@@ -74,6 +74,9 @@ hipError_t launch_delta_pair_log(const PairSide& A, const PairSide& B, const Out
 hipError_t launch_fold_log(int mode, const BatchView& dst, const SrcView& sb, const OutView& out, const Scratch& scr,
                            const MergeLogView& lg, const Work& wk, uint32_t* parts, uint32_t block_grid,
                            hipStream_t stream);
+hipError_t launch_apply_log(const BatchView& st, const TombView& tb, const ApplyOps& ops, const OutView& out,
+                            const TombOut& tout, bool has_tout, const MergeLogView& lg, const Work& wk,
+                            uint32_t* parts, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
                          uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
@@ -1495,6 +1498,71 @@ int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const c
     const ApplyOps av{ops->n_docs, ops->op_off, ops->kind, ops->keys, ops->doc_actor};
     rc = hip_err(launch_apply(view(state), tv, av, view(out), to, tomb_out != nullptr, make_work(ctx),
                               (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
+}
+
+// Logged local ops (apply_log.hip).  Workspace: the logged join's summary partial
+// sums.  The argument errors are apply's and the logged join's together.
+int crdt_awset_apply_log_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
+                               const crdt_op_batch* ops, const crdt_awset_out* out, const crdt_tomb_out* tomb_out,
+                               const crdt_merge_log* log, void* stream) {
+    if (!ctx || !batch_ptrs_ok(state) || !ops || !ops->op_off || !ops->doc_actor || !out_ptrs_ok(out))
+        return CRDT_E_INVALID;
+    if (ops->n_docs != state->n_docs) return CRDT_E_INVALID;
+    if (tombs && (!tombs->offsets || !tombs->keys || !tombs->actors || !tombs->counters)) return CRDT_E_INVALID;
+    if (tomb_out && (!tomb_out->offsets || !tomb_out->counts || !tomb_out->keys || !tomb_out->actors ||
+                     !tomb_out->counters))
+        return CRDT_E_INVALID;
+    const crdt_merge_log* l = log;
+    if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
+        !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
+        return CRDT_E_INVALID;
+    // No two written arrays start at one address, and no written array starts where
+    // an input array of the same kind starts.
+    struct Written {
+        const void* p;
+        int width;  // bytes per element: the array's kind
+    };
+    std::vector<Written> r = {{out->offsets, 4},    {out->counts, 4},      {out->vv, 8},          {out->keys, 8},
+                              {out->actors, 4},     {out->counters, 8},    {l->flags, 1},         {l->rem_offsets, 4},
+                              {l->rem_counts, 4},   {l->ups_offsets, 4},   {l->ups_counts, 4},    {l->rem_keys, 8},
+                              {l->rem_actors, 4},   {l->rem_counters, 8},  {l->ups_keys, 8},      {l->ups_actors, 4},
+                              {l->ups_counters, 8}};
+    if (tomb_out)
+        r.insert(r.end(), {{tomb_out->offsets, 4}, {tomb_out->counts, 4}, {tomb_out->keys, 8}, {tomb_out->actors, 4},
+                           {tomb_out->counters, 8}});
+    if (l->summary) r.push_back({l->summary, 4});
+    if (l->ups_kind) r.push_back({l->ups_kind, 1});
+    for (size_t i = 0; i < r.size(); ++i)
+        for (size_t j = i + 1; j < r.size(); ++j)
+            if (r[i].p == r[j].p) return CRDT_E_INVALID;
+    std::vector<const void*> in1 = {ops->kind}, in4 = {state->offsets, state->counts, state->actors, ops->op_off,
+                                                       ops->doc_actor},
+                             in8 = {state->keys, state->counters, state->vv, ops->keys};
+    if (tombs) {
+        in4.insert(in4.end(), {tombs->offsets, tombs->counts, tombs->actors});
+        in8.insert(in8.end(), {tombs->keys, tombs->counters});
+    }
+    for (const Written& w : r)
+        for (const void* q : w.width == 1 ? in1 : w.width == 4 ? in4 : in8)
+            if (q && w.p == q) return CRDT_E_INVALID;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (rc != CRDT_OK) return rc;
+    TombView tv{};
+    if (tombs) tv = TombView{tombs->offsets, tombs->counts, tombs->keys, tombs->actors, tombs->counters};
+    TombOut to{};
+    if (tomb_out) to = TombOut{tomb_out->offsets, tomb_out->counts, tomb_out->keys, tomb_out->actors, tomb_out->counters};
+    const ApplyOps av{ops->n_docs, ops->op_off, ops->kind, ops->keys, ops->doc_actor};
+    const MergeLogView lv{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
+                          l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
+                          l->ups_actors, l->ups_counters, l->ups_kind};
+    rc = hip_err(launch_apply_log(view(state), tv, av, view(out), to, tomb_out != nullptr, lv, make_work(ctx),
+                                  ctx->parts.as<uint32_t>(), (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 

@@ -832,6 +832,28 @@ func (e *Engine) FoldLog(mode int, dst *C.crdt_awset_batch, srcs *C.crdt_src_bat
 	return nil
 }
 
+// ApplyLog is crdt_awset_apply_async (batched Add / Del / AWSetDelta.Del on resident
+// documents) with the log of what the ops changed written beside the new state
+// (crdt_awset_apply_log_async): out and tombOut hold what the plain call writes;
+// log's removed list of document d starts at state.offsets[d] and holds the state
+// entries the ops removed with the dot they had, its upserted list starts at
+// ops.op_off[d] and holds the entries an Add left new (CRDT_DIFF_ADDED) or under
+// another dot (CRDT_DIFF_UPDATED). The log is crdt_awset_diff_async(state, out)'s
+// answer; tombstone changes are not part of it. A refused document's log is empty.
+// tombs and tombOut may be nil as in the plain call. With JoinLog and FoldLog an
+// index beside a replica follows local ops and merges alike. Asynchronous on
+// stream; device-side errors surface at the context's next sync.
+func (e *Engine) ApplyLog(state *C.crdt_awset_batch, tombs *C.crdt_tomb_batch, ops *C.crdt_op_batch,
+	out *C.crdt_awset_out, tombOut *C.crdt_tomb_out, log *MergeLog, stream unsafe.Pointer) error {
+	if state == nil || ops == nil || out == nil || log == nil {
+		return fmt.Errorf("ApplyLog: nil argument")
+	}
+	if rc := C.crdt_awset_apply_log_async(e.ctx, state, tombs, ops, out, tombOut, &log.Log, stream); rc != 0 {
+		return errOf("crdt_awset_apply_log_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- delta merge of a resident pair
 
 // DeltaJoin is (*AWSetDelta).Merge on resident replicas as they stand

@@ -54,6 +54,9 @@
  *   crdt_awset_fold_log_async
  *       the fold, in either mode, with the log of its net effect: what the
  *       receiver of a delta message and an N-way merge report to an index
+ *   crdt_awset_apply_log_async
+ *       the local ops with the same log: what Add / Del / (*AWSetDelta).Del
+ *       removed, added or moved to a new dot       awset.go:89-101
  *   crdt_awset_sources_async
  *       P resident replicas of every document gathered into the packed source
  *       batch the folds and the delta extraction read (no reference
@@ -1098,6 +1101,70 @@ int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, co
  * There is no _batch form. */
 int crdt_awset_fold_log_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
                               const crdt_awset_out* out, const crdt_merge_log* log, void* stream);
+
+/* ---- logged local ops: Add / Del / AWSetDelta.Del with the log of their effect --
+ * The logged calls above report what a merge changed.  The other half of what
+ * changes a resident set is its own replica's ops; this call is
+ * crdt_awset_apply_async with the log beside the new state, so that an index or a
+ * view kept beside a replica follows local ops and merges alike.  The host cannot
+ * derive the log from the op list: whether a Del hits a live key, which dot the
+ * removed entry had and whether an Add lands on a live key depend on the state.
+ * The state part: out and tomb_out hold what crdt_awset_apply_async writes for
+ * the same arguments -- offsets, counts, live entries, clocks and tombstones bit
+ * for bit, with its refusal rules and its tomb_out == NULL rule.
+ * The log is crdt_awset_diff_async(before = state, after = out)'s answer, per
+ * document d, in the inputs' own slot layouts (crdt_merge_log, above):
+ *   - removed: the live entries of state[d] whose key is not live in out[d], in
+ *     key order, with the dot they had in state.  They lie at state.offsets[d],
+ *     rem_counts[d] of them; rem_offsets repeats state.offsets (n_docs + 1
+ *     values); the capacity is the state's slots.
+ *   - upserted: the live entries of out[d] whose key was not live in state[d]
+ *     (CRDT_DIFF_ADDED) or was live there under a different (actor, counter)
+ *     (CRDT_DIFF_UPDATED), in key order, with their new dot.  They lie at
+ *     ops.op_off[d], ups_counts[d] of them; ups_offsets repeats op_off; the
+ *     capacity is the document's ops, which is enough: a document upserts at most
+ *     one entry per ADD op.  ups_kind is [n_ops] and indexed like ups_keys.
+ *   - flags[d] and summary as the diff writes them.  CRDT_DIFF_CLOCK is set iff
+ *     the document has an op that bumps the clock (ADD, DELTA_DEL): a DELTA_DEL
+ *     call none of whose keys is live is CLOCK and nothing else.
+ * Each list read as (offsets, counts, keys, actors, counters) is a valid
+ * crdt_tomb_batch.  Slots of a document at or past its count are unspecified;
+ * slots of other documents are never written.  No atomic decides a position: the
+ * bits are the same on every run.
+ * What "the diff's answer" means for an op list:
+ *   1. an ADD of a key live in the state is one UPDATED record, not a removal and
+ *      an add, also when a DEL of that key comes earlier in the list;
+ *   2. an ADD that mints the very dot the state's entry already has (the state
+ *      holds (actor, vv[actor] + k) and the k-th bump adds that key) is no
+ *      record: the dots are compared, and UPDATED is not set;
+ *   3. a key added and then deleted within the call that was not in the state
+ *      leaves no record; nor does a DEL or an ineffective DELTA_DEL_KEY of an
+ *      absent key.  A key of the state added and then deleted is one removed
+ *      record, with the state's dot;
+ *   4. tombstone changes are not part of this log: it is the diff of the entries.
+ *      tomb_out is the record of Deleted.
+ * A refused document (more than CRDT_MAX_OPS_PER_DOC ops, an unknown kind, a
+ * DELTA_DEL_KEY outside a call or without a tomb_out, a bump with actor >= R)
+ * comes out with count 0 and undefined slots, as in crdt_awset_apply_async; its
+ * log is empty -- rem_counts[d] = ups_counts[d] = 0, flags[d] = 0 -- and it adds
+ * nothing to summary.  Every other document's log is exact.
+ * Reported by crdt_ctx_sync, exactly as crdt_awset_apply_async reports them:
+ *   CRDT_E_ACTOR_RANGE  a bump with actor >= R
+ *   CRDT_E_INVALID      a malformed op list
+ *   CRDT_E_CAPACITY     a live count above its slots (clamped; the log is that
+ *                       of the clamped prefix)
+ * Returned by the call (CRDT_E_INVALID): everything crdt_awset_apply_async
+ * refuses; a NULL log or a NULL required field (summary and ups_kind may be
+ * NULL); two written arrays starting at one address; a written array starting
+ * where an input array of the same kind starts.
+ * n_docs == 0 launches nothing that reads documents; summary, when given, is
+ * zeroed.  Ordered after the context's previous call; no host sync, kernel nodes
+ * only, capturable.  Workspace: the logged join's fixed 64 KB of summary partial
+ * sums, which the context owns from its creation: nothing grows during a capture.
+ * There is no _batch form. */
+int crdt_awset_apply_log_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
+                               const crdt_op_batch* ops, const crdt_awset_out* out, const crdt_tomb_out* tomb_out,
+                               const crdt_merge_log* log, void* stream);
 
 /* ---- ingest sort ---------------------------------------------------------
  * The merge kernels need each document's keys strictly ascending; a producer
