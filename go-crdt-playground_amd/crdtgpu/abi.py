@@ -141,6 +141,16 @@ class CReplicaOut(ctypes.Structure):
     _fields_ = [("state", _vp), ("tombs", _vp), ("doc_actor", _vp)]
 
 
+class CReplicaInplace(ctypes.Structure):
+    _fields_ = [("n_docs", _u32), ("R", _u32), ("offsets", _vp), ("counts", _vp), ("keys", _vp), ("actors", _vp),
+                ("counters", _vp), ("vv", _vp), ("tomb_offsets", _vp), ("tomb_counts", _vp), ("tkeys", _vp),
+                ("tactors", _vp), ("tcounters", _vp), ("doc_actor", _vp)]
+
+
+class CSpillOut(ctypes.Structure):
+    _fields_ = [("spill_j", _vp), ("spill_doc", _vp), ("n_spill", _vp)]
+
+
 class CrdtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -240,6 +250,8 @@ def signatures():
         "crdt_replica_select_async": (ctypes.c_int, [_vp, P(CReplica), _vp, _vp, _u32, _u32, _u32, P(CReplicaOut), _vp]),
         "crdt_replica_scatter_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), _vp, _vp, _u32, _u32,
                                                       P(CReplicaOut), _vp]),
+        "crdt_replica_scatter_inplace_async": (ctypes.c_int, [_vp, P(CReplicaInplace), P(CReplica), _vp, _vp,
+                                                              P(CSpillOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

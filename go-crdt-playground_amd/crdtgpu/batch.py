@@ -12,7 +12,7 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, CMergeLog, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaOut, CSrcBatch,
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, CMergeLog, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaInplace, CReplicaOut, CSpillOut, CSrcBatch,
                   CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -442,6 +442,72 @@ class ReplicaBuffers:
                            _np(self.tombs.counters, U64)[:tt], counts=_np(self.tombs.counts, U32)[:n])
         da = None if self.doc_actor is None else _np(self.doc_actor, U32)[:n]
         return Replica(st, tb, 0, da)
+
+
+class InplaceTarget:
+    """A resident replica as the target of an in-place scatter (crdt_replica_inplace):
+    the state's arrays with its counts, the tombstones with theirs (None: the replica
+    keeps no Deleted) and the per-document actors (None: not written).  The offsets
+    are read, everything else is written where a document is placed.  of() views a
+    Replica, a ReplicaBuffers or an OutBuffers (with a TombBuffers) as it stands."""
+
+    def __init__(self, state, tombs=None, doc_actor=None):
+        self.state, self.tombs, self.doc_actor = state, tombs, doc_actor
+        if state.counts is None or (tombs is not None and tombs.counts is None):
+            raise ValueError("an in-place target needs counts: a document's length changes")
+
+    @staticmethod
+    def of(x, tombs=None, doc_actor=None, actors=True) -> "InplaceTarget":
+        if isinstance(x, InplaceTarget):
+            return x
+        if isinstance(x, (Replica, ReplicaBuffers)):
+            st = x.state if isinstance(x.state, AWSetBatch) else x.state.as_batch()
+            return InplaceTarget(st, x.tombs, x.doc_actor if actors else None)
+        if isinstance(x, OutBuffers):
+            return InplaceTarget(x.as_batch(), tombs, doc_actor)
+        return InplaceTarget(x, tombs, doc_actor)  # an AWSetBatch with counts
+
+    @property
+    def n_docs(self) -> int:
+        return self.state.n_docs
+
+    def c(self) -> CReplicaInplace:
+        s, t = self.state, self.tombs
+        tp = [ptr(getattr(t, f)) for f in ("offsets", "counts", "keys", "actors", "counters")] if t is not None \
+            else [None] * 5
+        return CReplicaInplace(s.n_docs, s.R, ptr(s.offsets), ptr(s.counts), ptr(s.keys), ptr(s.actors),
+                               ptr(s.counters), ptr(s.vv), *tp, ptr(self.doc_actor))
+
+    def as_replica(self, actor: int = 0) -> "Replica":
+        return Replica(self.state, self.tombs, actor, self.doc_actor)
+
+
+class SpillBuffers:
+    """The lists an in-place scatter writes (crdt_spill_out): the sub documents that
+    did not fit, ascending (spill_j), the replica document each names (spill_doc) and
+    their number (n_spill, one word); n_sub words each.  numpy, or torch on `device`.
+    spill_j / n_spill are the idx / n_idx of the select, spill_doc / n_spill those of
+    the scatter, that put the spilled documents back."""
+
+    def __init__(self, n_sub, device=None):
+        self.n_sub = int(n_sub)
+        if device is None:
+            self.spill_j, self.spill_doc = (np.zeros(max(n_sub, 1), U32) for _ in range(2))
+            self.n_spill = np.zeros(1, U32)
+        else:
+            import torch
+
+            self.spill_j, self.spill_doc = (torch.empty(max(n_sub, 1), dtype=torch.int32, device=device)
+                                            for _ in range(2))
+            self.n_spill = torch.empty(1, dtype=torch.int32, device=device)
+
+    def c(self) -> CSpillOut:
+        return CSpillOut(ptr(self.spill_j), ptr(self.spill_doc), ptr(self.n_spill))
+
+    def numpy(self):
+        """(spill_j, spill_doc) trimmed to *n_spill."""
+        n = int(_np(self.n_spill, U32)[0])
+        return _np(self.spill_j, U32)[:n].copy(), _np(self.spill_doc, U32)[:n].copy()
 
 
 class QueryBatch:

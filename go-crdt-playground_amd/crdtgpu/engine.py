@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, ReplicaBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -548,6 +548,51 @@ class Engine:
         self.replica_scatter_async(rep.to(dev), sub.to(dev), didx, out, dn)
         self.sync()
         return out.numpy()
+
+    def replica_scatter_inplace_async(self, target, sub, idx, spill: SpillBuffers, n_idx=None, stream=None):
+        """replica_scatter_async without the packed copy: sub doc j is written into the
+        slots `target` doc idx[j] already owns when its live entries and tombstones fit
+        them (count, clock, tombstone count and actor with it), and is listed in `spill`
+        otherwise; nothing else of target is touched (crdt_replica_scatter_inplace_async).
+        target: an InplaceTarget, or what InplaceTarget.of() views as one (a Replica with
+        counts, a ReplicaBuffers); sub: a Replica."""
+        ct = target if isinstance(target, ctypes.Structure) else _c(InplaceTarget.of(target))
+        cs, cp = _c(sub), _c(spill)
+        check(self._lib.crdt_replica_scatter_inplace_async(self._ctx, ctypes.byref(ct), ctypes.byref(cs), ptr(idx),
+                                                           ptr(n_idx), ctypes.byref(cp), _stream(stream)),
+              "crdt_replica_scatter_inplace_async")
+
+    def scatter_inplace_async(self, state, sub: AWSetBatch, idx, spill: SpillBuffers, n_idx=None, stream=None):
+        """replica_scatter_inplace_async for state-only batches: `state` (an AWSetBatch
+        with counts, or an OutBuffers) receives sub's documents in place; no tombstones,
+        no actors."""
+        tgt = InplaceTarget.of(state, actors=False)
+        self.replica_scatter_inplace_async(InplaceTarget(tgt.state), Replica(sub), idx, spill, n_idx, stream)
+
+    def replica_scatter_inplace(self, rep, sub, idx, n_idx=None):
+        """Host Replicas uploaded, sub scattered into rep in place on the device, and
+        downloaded: (rep as it then stands, same layout; spill_j; spill_doc)."""
+        import numpy as np
+        import torch
+
+        rep, sub = rep.numpy(), sub.numpy()
+        dev = torch.device("cuda", self.device)
+        if rep.state.counts is None:
+            o = rep.state.offsets
+            rep.state.counts = (o[1:] - o[:-1]).astype(np.uint32)
+        if rep.tombs is not None and rep.tombs.counts is None:
+            o = rep.tombs.offsets
+            rep.tombs.counts = (o[1:] - o[:-1]).astype(np.uint32)
+        drep = rep.to(dev)
+        spill = SpillBuffers(sub.n_docs, device=dev)
+        didx = torch.from_numpy(np.ascontiguousarray(idx, np.uint32).view(np.int32)).to(dev)
+        if didx.numel() == 0:
+            didx = torch.zeros(1, dtype=torch.int32, device=dev)
+        dn = None if n_idx is None else torch.tensor([int(n_idx)], dtype=torch.int32, device=dev)
+        self.replica_scatter_inplace_async(drep, sub.to(dev), didx, spill, dn)
+        self.sync()
+        sj, sd = spill.numpy()
+        return drep.numpy(), sj, sd
 
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),

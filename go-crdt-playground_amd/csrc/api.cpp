@@ -16,6 +16,7 @@
 
 #include "../../include/crdtgpu.h"
 #include "crdt_device.hpp"
+#include "replica.hpp"
 
 namespace crdt {
 hipError_t launch_join(const BatchView& dst, const BatchView& src, const OutView& out, const OutView* out2,
@@ -203,6 +204,7 @@ struct crdt_ctx {
     DevBuf ws;
     DevBuf worklist;
     DevBuf defer;  // folds: documents the lean pass leaves to the general kernel
+    DevBuf spill_parts;  // in-place replica scatter: the spill scan's partial sums, one word per 1,024 documents
     DevBuf parts;
     DevBuf scratch;  // fold block path ping-pong: keys | actors | counters
     // large-document join tiles (tile.hip): descriptors + look-back words for
@@ -326,6 +328,7 @@ int reserve_worklist(crdt_ctx* ctx, uint32_t n_docs) {
     // (two words at least: the replica scatter's two partial sums of a one-document replica)
     int rc = ctx->worklist.reserve(std::max<size_t>((size_t)n_docs, 2) * sizeof(uint32_t));
     if (rc == CRDT_OK) rc = ctx->defer.reserve(std::max<size_t>((size_t)n_docs, 2) * sizeof(uint32_t));
+    if (rc == CRDT_OK) rc = ctx->spill_parts.reserve(((size_t)n_docs / 1024 + 1) * sizeof(uint32_t));
     return rc;
 }
 
@@ -416,7 +419,7 @@ int crdt_ctx_create(int device, crdt_ctx** out) {
     crdt_ctx* ctx = new (std::nothrow) crdt_ctx();
     if (!ctx) return CRDT_E_NOMEM;
     ctx->device = device;
-    for (DevBuf* b : {&ctx->ws, &ctx->worklist, &ctx->defer, &ctx->parts, &ctx->scratch, &ctx->tile_desc, &ctx->tile_geo, &ctx->tile_flags,
+    for (DevBuf* b : {&ctx->ws, &ctx->worklist, &ctx->defer, &ctx->spill_parts, &ctx->parts, &ctx->scratch, &ctx->tile_desc, &ctx->tile_geo, &ctx->tile_flags,
                       &ctx->tile_slot, &ctx->tile_run, &ctx->sort_tmp, &ctx->sort_idx, &ctx->sort_ends})
         b->retired = &ctx->retired;
     for (auto& b : ctx->stage) b.retired = &ctx->retired;
@@ -456,6 +459,7 @@ void crdt_ctx_destroy(crdt_ctx* ctx) {
     ctx->ws.release();
     ctx->worklist.release();
     ctx->defer.release();
+    ctx->spill_parts.release();
     ctx->parts.release();
     ctx->scratch.release();
     for (DevBuf* b : {&ctx->tile_desc, &ctx->tile_geo, &ctx->tile_flags, &ctx->tile_slot, &ctx->tile_run,
@@ -1060,6 +1064,72 @@ int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crd
                                const uint32_t* n_idx, uint32_t entry_slots, uint32_t tomb_slots,
                                const crdt_replica_out* out, void* stream) {
     return replica_common(ctx, rep, sub, idx, n_idx, 0u, entry_slots, tomb_slots, out, true, stream);
+}
+
+// In-place replica scatter (replica_inplace.hip).  Workspace: the inverse map,
+// one word per replica document, in the worklist buffer; the verdicts, one word
+// per sub document, in the defer buffer; the spill scan's partial sums, one word
+// per 1,024 sub documents, in a buffer of their own (the other two are full at
+// max_docs documents): all three sized by crdt_ctx_reserve(max_docs, ..).
+int crdt_replica_scatter_inplace_async(crdt_ctx* ctx, const crdt_replica_inplace* rep, const crdt_replica* sub,
+                                       const uint32_t* idx, const uint32_t* n_idx, const crdt_spill_out* spill,
+                                       void* stream) {
+    if (!ctx || !rep || !sub || !batch_ptrs_ok(sub->state) || !idx || !spill) return CRDT_E_INVALID;
+    if (!spill->spill_j || !spill->spill_doc || !spill->n_spill) return CRDT_E_INVALID;
+    if (!rep->offsets || !rep->counts || !rep->keys || !rep->actors || !rep->counters || !rep->vv)
+        return CRDT_E_INVALID;
+    if (rep->R != sub->state->R || rep->R == 0 || rep->R > CRDT_MAX_R) return CRDT_E_INVALID;
+    const crdt_awset_batch* b = sub->state;
+    const crdt_tomb_batch* t = sub->tombs;
+    if (t && (!t->offsets || !rep->tomb_offsets || !rep->tkeys || !rep->tactors || !rep->tcounters))
+        return CRDT_E_INVALID;
+    if (rep->tomb_offsets && !rep->tomb_counts) return CRDT_E_INVALID;
+    // no written array of rep starts where an array of the same kind of sub starts
+    const uint32_t* in32[] = {b->offsets, b->counts, b->actors, sub->doc_actor, t ? t->offsets : nullptr,
+                              t ? t->counts : nullptr, t ? t->actors : nullptr};
+    const uint64_t* in64[] = {b->keys, b->counters, b->vv, t ? t->keys : nullptr, t ? t->counters : nullptr};
+    const uint32_t* out32[] = {rep->counts, rep->actors, rep->tomb_counts, rep->tactors, rep->doc_actor,
+                               spill->spill_j, spill->spill_doc, spill->n_spill};
+    const uint64_t* out64[] = {rep->keys, rep->counters, rep->vv, rep->tkeys, rep->tcounters};
+    for (const uint32_t* o : out32)
+        for (const uint32_t* i : in32)
+            if (o && o == i) return CRDT_E_INVALID;
+    for (const uint64_t* o : out64)
+        for (const uint64_t* i : in64)
+            if (o && o == i) return CRDT_E_INVALID;
+    InplaceArgs a{};
+    a.sub.n_docs = b->n_docs;
+    a.sub.actor = sub->actor;
+    a.sub.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
+    if (t) a.sub.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
+    a.sub.vv = b->vv;
+    a.sub.doc_actor = sub->doc_actor;
+    a.n_docs = rep->n_docs;
+    a.R = rep->R;
+    a.e = InplaceCols{rep->offsets, rep->counts, rep->keys, rep->actors, rep->counters};
+    if (rep->tomb_offsets)
+        a.t = InplaceCols{rep->tomb_offsets, rep->tomb_counts, rep->tkeys, rep->tactors, rep->tcounters};
+    a.vv = rep->vv;
+    a.doc_actor = rep->doc_actor;
+    a.idx = idx;
+    a.n_idx = n_idx;
+    a.spill_j = spill->spill_j;
+    a.spill_doc = spill->spill_doc;
+    a.n_spill = spill->n_spill;
+    int rc = set_device(ctx);
+    if (rc != CRDT_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    bool cap = false;
+    rc = enter(ctx, s, cap);
+    const size_t n_sub = b->n_docs;
+    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(rep->n_docs, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_sub, 1) * sizeof(uint32_t), cap);
+    if (rc == CRDT_OK) rc = grow(ctx->spill_parts, (n_sub / 1024 + 1) * sizeof(uint32_t), cap);
+    if (rc != CRDT_OK) return rc;
+    a.verdict = ctx->defer.as<uint32_t>();
+    rc = hip_err(launch_replica_inplace(a, ctx->worklist.as<uint32_t>(), ctx->spill_parts.as<uint32_t>(),
+                                        make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    return leave(ctx, s, cap, rc);
 }
 
 // Delta merge of a resident pair (delta_pair.hip).  Workspace: the join's

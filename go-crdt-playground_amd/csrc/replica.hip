@@ -47,6 +47,7 @@
 // word each per chunk of kRepScanChunk documents.
 #include "crdt_device.hpp"
 #include "merge_block.hpp"
+#include "replica.hpp"
 
 namespace crdt {
 
@@ -448,6 +449,19 @@ static bool cols_aligned(const SrcCols& c) {
     return aligned(c.keys, 16) && aligned(c.counters, 16) && aligned(c.actors, 8);
 }
 
+// The inverse map of a scatter, for launch_replica below and for the in-place
+// scatter (replica_inplace.hip): fill, then map.  n > 0.
+hipError_t launch_replica_map(const uint32_t* idx, const uint32_t* n_idx, uint32_t n_sub, uint32_t n, uint32_t* inv,
+                              uint32_t* status, uint32_t n_cu, hipStream_t stream) {
+    const uint32_t fgrid = min((n + (uint32_t)kRepNT - 1u) / (uint32_t)kRepNT, n_cu * 8u);
+    hipLaunchKernelGGL(replica_fill_kernel, dim3(fgrid), dim3(kRepNT), 0, stream, inv, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t mgrid = max(1u, min((uint32_t)(((uint64_t)n_sub + kRepNT - 1) / kRepNT), n_cu * 8u));
+    hipLaunchKernelGGL(replica_map_kernel, dim3(mgrid), dim3(kRepNT), 0, stream, idx, n_idx, n_sub, n, inv, status);
+    return hipGetLastError();
+}
+
 // a.inv != NULL: scatter (a.inv is also the n_out workspace words the map is built
 // in); parts_e, parts_t: one workspace word each per kRepScanChunk documents.
 // a.n_out == 0: only offsets[0] (= 0) of the entries and the tombstones are written.
@@ -457,16 +471,8 @@ hipError_t launch_replica(const ReplicaArgs& a, uint32_t* inv, uint32_t* parts_e
     const uint32_t n_parts = (uint32_t)(((uint64_t)n + kRepScanChunk - 1) / kRepScanChunk);
     hipError_t e = hipSuccess;
     if (n) {
-        if (inv) {
-            const uint32_t fgrid = min((n + (uint32_t)kRepNT - 1u) / (uint32_t)kRepNT, n_cu * 8u);
-            hipLaunchKernelGGL(replica_fill_kernel, dim3(fgrid), dim3(kRepNT), 0, stream, inv, n);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            const uint32_t mgrid =
-                max(1u, min((uint32_t)(((uint64_t)a.sub.n_docs + kRepNT - 1) / kRepNT), n_cu * 8u));
-            hipLaunchKernelGGL(replica_map_kernel, dim3(mgrid), dim3(kRepNT), 0, stream, a.idx, a.n_idx,
-                               a.sub.n_docs, n, inv, status);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
+        if (inv && (e = launch_replica_map(a.idx, a.n_idx, a.sub.n_docs, n, inv, status, n_cu, stream)) != hipSuccess)
+            return e;
         hipLaunchKernelGGL(replica_count_kernel, dim3(n_parts), dim3(kRepNT), 0, stream, a, parts_e, parts_t, status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }

@@ -17,6 +17,7 @@
 //	MakeDeltaMergeData   awset-delta_test.go:79-105  -> Engine.DeltaBatch (what to send a peer)
 //	resident replicas    (no reference counterpart)  -> Engine.SourcesBatch (fold / extraction input on the device)
 //	                                                    Engine.ReplicaSelect / ReplicaScatter (documents moved with Deleted and actors)
+//	                                                    Engine.ReplicaScatterInPlace (merged documents written back where they fit)
 //
 // AWSetDelta lives in a _test.go file of the reference, invisible to importers,
 // so this package defines it (with Del and Clone, awset-delta_test.go:9-49).
@@ -765,6 +766,61 @@ func (e *Engine) ReplicaScatter(rep, sub *Replica, idx, nIdx *C.uint32_t, entryS
 	if rc := C.crdt_replica_scatter_async(e.ctx, cr, cs, idx, nIdx, C.uint32_t(entrySlots),
 		C.uint32_t(tombSlots), co, stream); rc != 0 {
 		return errOf("crdt_replica_scatter_async", rc)
+	}
+	return nil
+}
+
+// ReplicaInPlace is a device-resident replica updated in place: the state's
+// arrays with its counts (StateOut; every array but the offsets is written), its
+// tombstones with their counts (Tombs, nil: the replica keeps none) and one actor
+// per document (DocActor, nil: actors not written). Every pointer is a device
+// pointer.
+type ReplicaInPlace struct {
+	StateOut C.crdt_awset_out
+	NDocs, R uint32
+	Tombs    *C.crdt_tomb_out
+	DocActor *C.uint32_t
+}
+
+// SpillOut receives the sub documents an in-place scatter could not place:
+// SpillJ their indices in sub, ascending, SpillDoc the replica document each
+// names, NSpill their number (one device word). Each list holds as many words as
+// sub has documents.
+type SpillOut struct {
+	SpillJ, SpillDoc, NSpill *C.uint32_t
+}
+
+// ReplicaScatterInPlace writes each document of sub into the slots its replica
+// document idx[j] already owns when its live entries and tombstones fit them,
+// and lists it in spill otherwise (crdt_replica_scatter_inplace_async). Nothing
+// else of rep is touched: no packed copy of the replica is made, which is what
+// ReplicaScatter costs. ReplicaSelect(sub, spill.SpillJ, spill.NSpill, ..)
+// followed by ReplicaScatter(rep, that, spill.SpillDoc, spill.NSpill, ..) puts
+// the spilled documents back. Asynchronous on stream; device-side errors surface
+// at the context's next sync.
+func (e *Engine) ReplicaScatterInPlace(rep *ReplicaInPlace, sub *Replica, idx, nIdx *C.uint32_t, spill *SpillOut,
+	stream unsafe.Pointer) error {
+	var a arena
+	defer a.free()
+	cs := replicaC(&a, sub)
+	pr := a.alloc(int(unsafe.Sizeof(C.crdt_replica_inplace{})))
+	pp := a.alloc(int(unsafe.Sizeof(C.crdt_spill_out{})))
+	if a.err != nil {
+		return a.err
+	}
+	ri := C.crdt_replica_inplace{n_docs: C.uint32_t(rep.NDocs), R: C.uint32_t(rep.R), offsets: rep.StateOut.offsets,
+		counts: rep.StateOut.counts, keys: rep.StateOut.keys, actors: rep.StateOut.actors, counters: rep.StateOut.counters,
+		vv: rep.StateOut.vv, doc_actor: rep.DocActor}
+	if rep.Tombs != nil {
+		ri.tomb_offsets, ri.tomb_counts = rep.Tombs.offsets, rep.Tombs.counts
+		ri.tkeys, ri.tactors, ri.tcounters = rep.Tombs.keys, rep.Tombs.actors, rep.Tombs.counters
+	}
+	sp := C.crdt_spill_out{spill_j: spill.SpillJ, spill_doc: spill.SpillDoc, n_spill: spill.NSpill}
+	*(*C.crdt_replica_inplace)(pr) = ri
+	*(*C.crdt_spill_out)(pp) = sp
+	if rc := C.crdt_replica_scatter_inplace_async(e.ctx, (*C.crdt_replica_inplace)(pr), cs, idx, nIdx,
+		(*C.crdt_spill_out)(pp), stream); rc != 0 {
+		return errOf("crdt_replica_scatter_inplace_async", rc)
 	}
 	return nil
 }

@@ -69,6 +69,10 @@
  *       select and scatter over a whole replica: the documents move with
  *       their Deleted tombstones and actors, which is what a sparse delta
  *       round and a sparse apply need (no reference counterpart)
+ *   crdt_replica_scatter_inplace_async
+ *       replaces crdt_replica_scatter_async in those rounds: a merged document
+ *       is written into the slots its document already owns when it fits, and
+ *       named in a spill list otherwise (no reference counterpart)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -933,6 +937,84 @@ int crdt_replica_select_async(crdt_ctx* ctx, const crdt_replica* rep, const uint
 int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub,
                                const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */,
                                uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out, void* stream);
+
+/* ---- in-place replica scatter: merged documents written back where they fit ----
+ * Replaces crdt_replica_scatter_async (and, for state-only batches,
+ * crdt_awset_scatter_async) in the sparse rounds.  Those calls write a new, packed
+ * copy of the whole replica, so putting 5 % of the documents back costs a pass
+ * over 100 %.  This call writes each merged document into the slots its document
+ * already owns when it fits, touches nothing else, and names the documents that
+ * do not fit, so that only those take the packed scatter.  Every merge output
+ * sits at capacity offsets and so carries the slack this needs.
+ * Document mapping: crdt_replica_scatter_async's.  Every j < *n_idx with
+ * d = idx[j] takes part (n_idx == NULL: sub->state->n_docs).  Reported by
+ * crdt_ctx_sync:
+ *   *n_idx > sub n_docs   clamped, CRDT_E_CAPACITY
+ *   idx[j] >= n_docs      CRDT_E_INVALID; that sub document is ignored
+ *   two j name one document: CRDT_E_INVALID; the lowest j supplies it, the others
+ *                         are ignored and never listed as spilled
+ *   a sub live count above its slots, entries or tombstones: clamped,
+ *                         CRDT_E_CAPACITY
+ * Verdict per winning j, all or nothing.  ne, nt: sub document j's clamped live
+ * entry and tombstone counts (nt = 0 when sub->tombs == NULL); ce = offsets[d+1] -
+ * offsets[d], ct the same over tomb_offsets (0 when tomb_offsets == NULL).
+ *   Placed, iff ne <= ce and nt <= ct: the live entries are copied verbatim to
+ *     offsets[d] + i and counts[d] = ne; the R clock words are copied; the live
+ *     tombstones are copied to tomb_offsets[d] + i and tomb_counts[d] = nt (0 when
+ *     the replica keeps tombstones and sub has none); doc_actor[d], when given,
+ *     becomes sub's actor for j (its doc_actor[j], or its uniform actor).
+ *   Spilled, otherwise: nothing of document d is written (no entries, tombstones,
+ *     count, clock or actor); j is appended to spill_j and d to spill_doc.  A
+ *     spill is not an error.
+ * Never written: offsets and tomb_offsets; every word of every document not
+ * placed; in a placed document, every slot at or past its new count.  The
+ * replica after the call is bit-identical to the replica before it except for
+ * the live prefixes, counts, clocks and actors of the placed documents.
+ * Spill lists: spill_j ascending, spill_doc[i] = idx[spill_j[i]], *n_spill exact;
+ * no atomic decides a position, so the bits are the same on every run.  They
+ * feed the existing calls with no host round trip:
+ * crdt_replica_select_async(sub, spill_j, n_spill, ..) followed by
+ * crdt_replica_scatter_async(rep, that, spill_doc, n_spill, ..) is the fallback
+ * for what did not fit (with *n_spill == 0 that scatter is the identity); a
+ * caller reads back the 4 bytes of n_spill to skip it.
+ * Returned by the call (CRDT_E_INVALID): a NULL argument or a NULL required
+ * array (counts included); R different between rep and sub, or out of range;
+ * sub->tombs != NULL while rep->tomb_offsets == NULL; a tombstone batch without
+ * offsets; a written array of rep starting where an array of the same kind of
+ * sub starts; idx or a spill array NULL.
+ * Empty calls: with n_docs == 0 or no sub documents, *n_spill = 0 is written and
+ * nothing that reads documents is launched.
+ * State-only batches: a crdt_replica with tombs == NULL onto a target with
+ * tomb_offsets == NULL and doc_actor == NULL.
+ * Workspace: the inverse map (one word per replica document), one verdict word
+ * per sub document and the spill scan's partial sums (one word per 1,024 sub
+ * documents), in context buffers that crdt_ctx_reserve(max_docs, ..) sizes for
+ * max_docs >= both document counts: no allocation on a reserved context,
+ * CRDT_E_WORKSPACE when one would have to grow during a graph capture.  No host
+ * sync, kernel nodes only, capturable; ordered after the context's previous call
+ * like every entry point; errors reported by crdt_ctx_sync. */
+typedef struct {                 /* a resident replica updated in place */
+    uint32_t n_docs; uint32_t R;
+    const uint32_t* offsets;     /* [n_docs+1] slot bounds: read, never written        */
+    uint32_t* counts;            /* [n_docs]   required (a document's length changes)  */
+    uint64_t* keys; uint32_t* actors; uint64_t* counters;
+    uint64_t* vv;                /* [n_docs*R] */
+    const uint32_t* tomb_offsets;/* [n_docs+1], or NULL: the replica keeps no Deleted  */
+    uint32_t* tomb_counts;       /* required when tomb_offsets != NULL                 */
+    uint64_t* tkeys; uint32_t* tactors; uint64_t* tcounters;
+    uint32_t* doc_actor;         /* [n_docs] or NULL: actors not written               */
+} crdt_replica_inplace;
+
+typedef struct {                 /* written; each list holds sub->state->n_docs words  */
+    uint32_t* spill_j;           /* sub documents that did not fit, ascending          */
+    uint32_t* spill_doc;         /* idx[spill_j[i]]: the replica document each names   */
+    uint32_t* n_spill;           /* device, [1]                                        */
+} crdt_spill_out;
+
+int crdt_replica_scatter_inplace_async(crdt_ctx* ctx, const crdt_replica_inplace* rep,
+                                       const crdt_replica* sub, const uint32_t* idx,
+                                       const uint32_t* n_idx /* device, [1], or NULL */,
+                                       const crdt_spill_out* spill, void* stream);
 
 /* ---- delta merge of a resident replica pair ---------------------------------
  * (*AWSetDelta).Merge (awset-delta_test.go:51-65) applied to replicas in their
