@@ -11,7 +11,7 @@ from .abi import (CRDT_E_ACTOR_RANGE, CRDT_E_CAPACITY, CRDT_E_DUP_KEY, CRDT_E_HI
                   CRDT_CMP_KEYS, CRDT_CMP_DOTS, CRDT_CMP_A_AHEAD, CRDT_CMP_B_AHEAD, CRDT_DIG_ELEMENTS, CRDT_DIG_STATE,
                   CRDT_DIFF_REMOVED, CRDT_DIFF_ADDED, CRDT_DIFF_UPDATED, CRDT_DIFF_CLOCK,
                   CrdtError, LIB_PATH, header_functions, lib, strerror)
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers,  # noqa: F401
-                    TombBatch, TombBuffers)
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers,  # noqa: F401
+                    TombBatch, TombBuffers, repack_slots)
 from .engine import (Engine, comm_unique_id, digest_host, dump_batch, format_doc, global_context_allreduce,  # noqa: F401
                      load_batch, validate, validate_src)

@@ -151,6 +151,10 @@ class CSpillOut(ctypes.Structure):
     _fields_ = [("spill_j", _vp), ("spill_doc", _vp), ("n_spill", _vp)]
 
 
+class CHeadroom(ctypes.Structure):
+    _fields_ = [("min_spare", _u32), ("num", _u32), ("shift", _u32), ("align", _u32)]
+
+
 class CrdtError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -252,6 +256,9 @@ def signatures():
                                                       P(CReplicaOut), _vp]),
         "crdt_replica_scatter_inplace_async": (ctypes.c_int, [_vp, P(CReplicaInplace), P(CReplica), _vp, _vp,
                                                               P(CSpillOut), _vp]),
+        "crdt_headroom_capacity": (_u32, [P(CHeadroom), _u32]),
+        "crdt_replica_repack_async": (ctypes.c_int, [_vp, P(CReplica), P(CReplica), _vp, _vp, _u32, P(CHeadroom),
+                                                     P(CHeadroom), _u32, _u32, P(CReplicaOut), _vp]),
         "crdt_vv_max_async": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _vp]),
         "crdt_causal_context_async": (ctypes.c_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
         "crdt_gen_pair_async": (ctypes.c_int, [_vp, _u64, _u32, P(CAWSetOut), P(CAWSetOut), _vp]),

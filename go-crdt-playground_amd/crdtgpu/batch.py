@@ -12,7 +12,9 @@ import ctypes
 
 import numpy as np
 
-from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, CMergeLog, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaInplace, CReplicaOut, CSpillOut, CSrcBatch,
+import dataclasses
+
+from .abi import (CAWSetBatch, CAWSetOut, CCompareOut, CDeltaOut, CDiffOut, CHeadroom, CMergeLog, COpBatch, CQueryBatch, CQueryOut, CReplica, CReplicaInplace, CReplicaOut, CSpillOut, CSrcBatch,
                   CTombBatch, CTombOut)
 
 U32, U64 = np.uint32, np.uint64
@@ -442,6 +444,43 @@ class ReplicaBuffers:
                            _np(self.tombs.counters, U64)[:tt], counts=_np(self.tombs.counts, U32)[:n])
         da = None if self.doc_actor is None else _np(self.doc_actor, U32)[:n]
         return Replica(st, tb, 0, da)
+
+
+@dataclasses.dataclass(frozen=True)
+class Headroom:
+    """The layout policy of a replica repack (crdt_headroom): a document with n live
+    slots owns round_up(n + max(min_spare, (n * num) >> shift), align) slots.  The
+    default is packed.  The expression itself lives in the library
+    (crdt_headroom_capacity), and capacity() asks it."""
+
+    min_spare: int = 0
+    num: int = 0
+    shift: int = 0
+    align: int = 1
+
+    def c(self) -> CHeadroom:
+        return CHeadroom(self.min_spare, self.num, self.shift, self.align)
+
+    def capacity(self, n: int) -> int:
+        from . import abi
+
+        h = self.c()
+        return int(abi.lib().crdt_headroom_capacity(ctypes.byref(h), int(n)))
+
+    def total(self, counts) -> int:
+        """Slots a repack asks for, for a host-known vector of live counts (one capacity
+        per distinct count from the library; the sum is not saturated)."""
+        vals, reps = np.unique(np.asarray(counts, U32), return_counts=True)
+        return sum(self.capacity(int(v)) * int(r) for v, r in zip(vals, reps))
+
+
+def repack_slots(entry_counts, tomb_counts=None, entry_room=None, tomb_room=None):
+    """(entry_slots, tomb_slots) that crdt_replica_repack_async needs for output
+    documents with these live counts (host arrays, one per output document; empty
+    documents count with 0).  tomb_counts None: every document has no tombstone."""
+    ec = np.asarray(entry_counts, U32)
+    tc = np.zeros(len(ec), U32) if tomb_counts is None else np.asarray(tomb_counts, U32)
+    return (entry_room or Headroom()).total(ec), (tomb_room or Headroom()).total(tc)
 
 
 class InplaceTarget:

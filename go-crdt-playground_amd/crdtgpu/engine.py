@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -593,6 +593,68 @@ class Engine:
         self.sync()
         sj, sd = spill.numpy()
         return drep.numpy(), sj, sd
+
+    def replica_repack_async(self, rep, out: ReplicaBuffers, sub=None, idx=None, n_idx=None, n_out=None,
+                             entry_room: Headroom = None, tomb_room: Headroom = None, entry_slots=None,
+                             tomb_slots=None, stream=None):
+        """replica_select_async (sub None) or replica_scatter_async (sub a Replica, idx its
+        documents' places) writing a layout with headroom: out doc j owns
+        entry_room.capacity(live entries) entry slots and tomb_room.capacity(live
+        tombstones) tombstone slots, offsets their prefix, counts the live counts, and
+        nothing at or past a live count is written (crdt_replica_repack_async).  A room
+        of None is packed.  out is a Replica (out.as_replica()) and an in-place target
+        (InplaceTarget.of(out)) as it stands."""
+        cr, co = _c(rep), _c(out)
+        cs = _c(sub) if sub is not None else None
+        n_out = (out.n_docs if sub is None else rep.n_docs) if n_out is None else n_out
+        entry_slots = out.entry_slots if entry_slots is None else entry_slots
+        tomb_slots = out.tomb_slots if tomb_slots is None else tomb_slots
+        er = entry_room.c() if entry_room is not None else None
+        tr = tomb_room.c() if tomb_room is not None else None
+        check(self._lib.crdt_replica_repack_async(self._ctx, ctypes.byref(cr), ctypes.byref(cs) if cs is not None else None,
+                                                  ptr(idx), ptr(n_idx), int(n_out),
+                                                  ctypes.byref(er) if er is not None else None,
+                                                  ctypes.byref(tr) if tr is not None else None, int(entry_slots),
+                                                  int(tomb_slots), ctypes.byref(co), _stream(stream)),
+              "crdt_replica_repack_async")
+
+    def replica_repack(self, rep, sub=None, idx=None, n_idx=None, n_out=None, entry_room=None, tomb_room=None):
+        """Host Replicas uploaded, repacked on the device and downloaded: (Replica, code).
+        The Replica keeps its layout (offsets the prefix of the capacities, columns as
+        long as the capacity totals, slack zeroed by the allocation), so
+        InplaceTarget.of() takes it as it stands; code is what crdt_ctx_sync reports
+        (0: CRDT_OK).  The buffers are sized from a first call with no slots, which
+        writes the live counts."""
+        import numpy as np
+        import torch
+
+        rep = rep.numpy()
+        sub = sub.numpy() if sub is not None else None
+        dev = torch.device("cuda", self.device)
+        if sub is not None:
+            n_out = rep.n_docs
+        else:
+            n_out = (rep.n_docs if idx is None else len(idx)) if n_out is None else int(n_out)
+        tombs = rep.tombs is not None or (sub is not None and sub.tombs is not None)
+        didx = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, np.uint32).view(np.int32)).to(dev)
+        if didx is not None and didx.numel() == 0:
+            didx = torch.zeros(1, dtype=torch.int32, device=dev)
+        dn = None if n_idx is None else torch.tensor([int(n_idx)], dtype=torch.int32, device=dev)
+        drep, dsub = rep.to(dev), sub.to(dev) if sub is not None else None
+        kw = dict(sub=dsub, idx=didx, n_idx=dn, n_out=n_out, entry_room=entry_room, tomb_room=tomb_room)
+        probe = ReplicaBuffers(n_out, rep.state.R, 0, 0, device=dev, tombs=tombs)
+        self.replica_repack_async(drep, probe, **kw)
+        self._lib.crdt_ctx_sync(self._ctx, None)  # (CRDT_E_CAPACITY by construction: nothing fits no slots)
+        es = (entry_room or Headroom()).total(_np(probe.state.counts, np.uint32)[:n_out])
+        ts = (tomb_room or Headroom()).total(_np(probe.tombs.counts, np.uint32)[:n_out]) if tombs else 0
+        out = ReplicaBuffers(n_out, rep.state.R, min(es, 0xFFFFFFFF), min(ts, 0xFFFFFFFF), device=dev, tombs=tombs)
+        for b in (out.state, out.tombs):
+            if b is not None:
+                for f in ("keys", "actors", "counters"):
+                    getattr(b, f).zero_()
+        self.replica_repack_async(drep, out, **kw)
+        code = int(self._lib.crdt_ctx_sync(self._ctx, None))
+        return out.numpy(), code
 
     def vv_min_async(self, dst, src, n: int, stream=None):
         check(self._lib.crdt_vv_min_async(self._ctx, ptr(dst), ptr(src), int(n), _stream(stream)),

@@ -16,6 +16,7 @@
 
 #include "../../include/crdtgpu.h"
 #include "crdt_device.hpp"
+#include "headroom.hpp"
 #include "replica.hpp"
 
 namespace crdt {
@@ -966,9 +967,12 @@ int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n
 // scatter keeps its inverse map (one word per document) in the worklist buffer
 // and both partial arrays in the defer buffer (2 * ceil(n / 1,024) <= max(n, 2)
 // words), which is what crdt_ctx_reserve(max_docs, ..) sizes them for.
+// room != NULL: the repack (replica_repack.hip) with the entry policy room[0] and
+// the tombstone policy room[1]; same arguments, checks and workspace.
 static int replica_common(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
                           const uint32_t* n_idx, uint32_t n_out, uint32_t entry_slots, uint32_t tomb_slots,
-                          const crdt_replica_out* out, bool scatter, void* stream) {
+                          const crdt_replica_out* out, bool scatter, void* stream,
+                          const crdt_headroom* room = nullptr) {
     if (!ctx || !rep || !batch_ptrs_ok(rep->state) || !out || !out_ptrs_ok(out->state)) return CRDT_E_INVALID;
     if (scatter && (!sub || !batch_ptrs_ok(sub->state) || !idx || sub->state->R != rep->state->R))
         return CRDT_E_INVALID;
@@ -1050,7 +1054,11 @@ static int replica_common(crdt_ctx* ctx, const crdt_replica* rep, const crdt_rep
         parts_e = ctx->worklist.as<uint32_t>();
         parts_t = ctx->defer.as<uint32_t>();
     }
-    rc = hip_err(launch_replica(a, inv, parts_e, parts_t, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    if (room)
+        rc = hip_err(launch_replica_repack(RepackArgs{a, room[0], room[1]}, inv, parts_e, parts_t,
+                                           make_work(ctx).status, (uint32_t)ctx->n_cu, s));
+    else
+        rc = hip_err(launch_replica(a, inv, parts_e, parts_t, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
     return leave(ctx, s, cap, rc);
 }
 
@@ -1064,6 +1072,25 @@ int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crd
                                const uint32_t* n_idx, uint32_t entry_slots, uint32_t tomb_slots,
                                const crdt_replica_out* out, void* stream) {
     return replica_common(ctx, rep, sub, idx, n_idx, 0u, entry_slots, tomb_slots, out, true, stream);
+}
+
+// The headroom policy's capacity: headroom_cap64 (headroom.hpp) saturated, the one
+// definition the repack kernels share.  A NULL policy is packed.
+uint32_t crdt_headroom_capacity(const crdt_headroom* h, uint32_t n) {
+    bool sat = false;
+    return headroom_cap(h ? *h : kHeadroomPacked, n, &sat);
+}
+
+// Replica repack (replica_repack.hip): select's arguments when sub == NULL,
+// scatter's otherwise, and everything replica_common checks and sizes for them.
+int crdt_replica_repack_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
+                              const uint32_t* n_idx, uint32_t n_out, const crdt_headroom* entry_room,
+                              const crdt_headroom* tomb_room, uint32_t entry_slots, uint32_t tomb_slots,
+                              const crdt_replica_out* out, void* stream) {
+    const crdt_headroom room[2] = {entry_room ? *entry_room : kHeadroomPacked, tomb_room ? *tomb_room : kHeadroomPacked};
+    if (!headroom_ok(room[0]) || !headroom_ok(room[1])) return CRDT_E_INVALID;
+    if (sub && (!rep || !rep->state || n_out != rep->state->n_docs)) return CRDT_E_INVALID;
+    return replica_common(ctx, rep, sub, idx, n_idx, n_out, entry_slots, tomb_slots, out, sub != nullptr, stream, room);
 }
 
 // In-place replica scatter (replica_inplace.hip).  Workspace: the inverse map,

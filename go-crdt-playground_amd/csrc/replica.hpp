@@ -41,4 +41,17 @@ struct InplaceArgs {
 hipError_t launch_replica_inplace(const InplaceArgs& a, uint32_t* inv, uint32_t* parts, uint32_t* status,
                                   uint32_t n_cu, hipStream_t stream);
 
+// Replica repack (crdt_replica_repack_async; replica_repack.hip): select's or
+// scatter's arguments and the two headroom policies (NULL already replaced by
+// the packed policy).
+struct RepackArgs {
+    ReplicaArgs s;
+    crdt_headroom er, tr;
+};
+
+// launch_replica's workspace and conventions (replica.hip): a.s.inv != NULL is the
+// scatter mapping, a.s.n_out == 0 writes offsets[0] = 0 alone.
+hipError_t launch_replica_repack(const RepackArgs& a, uint32_t* inv, uint32_t* parts_e, uint32_t* parts_t,
+                                 uint32_t* status, uint32_t n_cu, hipStream_t stream);
+
 }  // namespace crdt

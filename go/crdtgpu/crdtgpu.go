@@ -825,6 +825,68 @@ func (e *Engine) ReplicaScatterInPlace(rep *ReplicaInPlace, sub *Replica, idx, n
 	return nil
 }
 
+// Headroom is the layout policy of ReplicaRepack (crdt_headroom): a document with
+// n live slots owns round_up(n + max(MinSpare, (n*Num)>>Shift), Align) slots.
+// Align is a power of two from 1 to 64 and Shift at most 31. A nil *Headroom is
+// the packed layout.
+type Headroom struct {
+	MinSpare, Num, Shift, Align uint32
+}
+
+func headroomC(a *arena, h *Headroom) *C.crdt_headroom {
+	if h == nil {
+		return nil
+	}
+	ph := a.alloc(int(unsafe.Sizeof(C.crdt_headroom{})))
+	if a.err != nil {
+		return nil
+	}
+	ch := C.crdt_headroom{min_spare: C.uint32_t(h.MinSpare), num: C.uint32_t(h.Num), shift: C.uint32_t(h.Shift),
+		align: C.uint32_t(h.Align)}
+	*(*C.crdt_headroom)(ph) = ch
+	return (*C.crdt_headroom)(ph)
+}
+
+// Capacity is the slot count the policy gives a document with n live slots
+// (crdt_headroom_capacity): the library's own expression, saturated at 2^32 - 1.
+func (h *Headroom) Capacity(n uint32) uint32 {
+	if h == nil {
+		return uint32(C.crdt_headroom_capacity(nil, C.uint32_t(n)))
+	}
+	ch := C.crdt_headroom{min_spare: C.uint32_t(h.MinSpare), num: C.uint32_t(h.Num), shift: C.uint32_t(h.Shift),
+		align: C.uint32_t(h.Align)}
+	return uint32(C.crdt_headroom_capacity(&ch, C.uint32_t(n)))
+}
+
+// ReplicaRepack is ReplicaSelect (sub nil) or ReplicaScatter (sub given; nOut must
+// be rep's document count) writing a layout with spare slots
+// (crdt_replica_repack_async): document j of out owns entryRoom.Capacity(live
+// entries) entry slots and tombRoom.Capacity(live tombstones) tombstone slots, the
+// offsets are the prefix of those capacities, the counts are the live counts, and
+// no slot at or past a live count is written. out is a replica as it stands and a
+// ReplicaInPlace target with no copy, so a replica that has spilled regains the
+// room ReplicaScatterInPlace needs. Asynchronous on stream; device-side errors
+// surface at the context's next sync.
+func (e *Engine) ReplicaRepack(rep, sub *Replica, idx, nIdx *C.uint32_t, nOut uint32, entryRoom, tombRoom *Headroom,
+	entrySlots, tombSlots uint32, out *ReplicaOut, stream unsafe.Pointer) error {
+	var a arena
+	defer a.free()
+	cr, co := replicaC(&a, rep), replicaOutC(&a, out)
+	var cs *C.crdt_replica
+	if sub != nil {
+		cs = replicaC(&a, sub)
+	}
+	er, tr := headroomC(&a, entryRoom), headroomC(&a, tombRoom)
+	if a.err != nil {
+		return a.err
+	}
+	if rc := C.crdt_replica_repack_async(e.ctx, cr, cs, idx, nIdx, C.uint32_t(nOut), er, tr, C.uint32_t(entrySlots),
+		C.uint32_t(tombSlots), co, stream); rc != 0 {
+		return errOf("crdt_replica_repack_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- logged join
 
 // MergeLog is the device storage a logged join writes beside the merged state

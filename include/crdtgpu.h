@@ -73,6 +73,10 @@
  *       replaces crdt_replica_scatter_async in those rounds: a merged document
  *       is written into the slots its document already owns when it fits, and
  *       named in a spill list otherwise (no reference counterpart)
+ *   crdt_replica_repack_async / crdt_headroom_capacity
+ *       the same select or scatter writing a layout with spare slots per
+ *       document, so that the in-place scatter finds room (no reference
+ *       counterpart)
  *   crdt_global_context_allreduce / crdt_context_allreduce_async
  *       that summary combined across GPUs: RCCL all-reduce(max, u64)
  *       (the reference's counterpart is the CPU max over
@@ -1015,6 +1019,59 @@ int crdt_replica_scatter_inplace_async(crdt_ctx* ctx, const crdt_replica_inplace
                                        const crdt_replica* sub, const uint32_t* idx,
                                        const uint32_t* n_idx /* device, [1], or NULL */,
                                        const crdt_spill_out* spill, void* stream);
+
+/* ---- replica repack with headroom: the layout policy of the in-place scatter ----
+ * crdt_replica_select_async and crdt_replica_scatter_async write "packed with no
+ * slack", and they are the fallback for a spill of
+ * crdt_replica_scatter_inplace_async: a replica that has spilled comes back with
+ * no spare slot and spills again.  This call is the same select (sub == NULL) or
+ * scatter (sub != NULL) writing a layout that leaves every document spare slots,
+ * by a policy the caller states.
+ * Capacity of a document with n live slots (part of the ABI, like the digest):
+ *     cap(n) = round_up(n + max(min_spare, (n * num) >> shift), align)
+ * computed in 64 bits; a value above 2^32 - 1 saturates to 2^32 - 1.
+ * crdt_headroom_capacity is that expression on the host (pure, no context); the
+ * kernels evaluate the same inline.  A NULL policy is {0, 0, 0, 1}: packed.
+ * entry_room sizes the entries, tomb_room the tombstones, independently.
+ * Document mapping: with sub == NULL crdt_replica_select_async's (idx, n_idx,
+ * n_out, empty documents beyond *n_idx); with sub != NULL
+ * crdt_replica_scatter_async's (the inverse map, the lowest j wins), and n_out
+ * must equal rep->state->n_docs.  An empty document gets cap(0) slots too: it can
+ * take an Add.
+ * Layout written: offsets is the exclusive prefix of the capacities and
+ * offsets[n_out] their total; counts[d] is the live count (always written); the
+ * live prefix, clock, tombstone live prefix and actor are what select and scatter
+ * copy.  out->tombs, when passed, gets the tombstone layout by tomb_room even when
+ * no input replica has tombs (cap(0) slots each).  Every slot at or past a
+ * document's live count is never written.  With offsets[0] = 0 every document
+ * starts at a multiple of align.  The output is a crdt_replica as it stands, and a
+ * crdt_replica_inplace target (offsets, counts, columns, clock, tombstone arrays,
+ * doc_actor) with no copy.  With both policies NULL every word the select and
+ * scatter calls write is written bit-identically.
+ * Reported by crdt_ctx_sync: the clamps and index errors of select and scatter,
+ * unchanged; CRDT_E_CAPACITY when the capacity total of the entries exceeds
+ * entry_slots or that of the tombstones tomb_slots (independently): nothing is
+ * written at or past the exceeded array's slots, offsets and totals stay the
+ * exact prefix modulo 2^32 (running totals in 64 bits), so a caller can size its
+ * buffers from a first call; CRDT_E_CAPACITY when one document's cap(n) saturates.
+ * Returned by the call (CRDT_E_INVALID): align not a power of two in 1..64;
+ * shift > 31; sub != NULL and n_out != rep->state->n_docs; everything the select
+ * and scatter forms return it for.
+ * Empty calls, workspace (partial sums per 1,024 documents; the inverse map for the
+ * scatter mapping; crdt_ctx_reserve sizing; CRDT_E_WORKSPACE under capture) and
+ * ordering are select's and scatter's: kernel nodes only, capturable.  There is no
+ * _batch form. */
+typedef struct {                 /* capacity of a document with n live slots          */
+    uint32_t min_spare;          /* at least this many spare slots                     */
+    uint32_t num;                /* and at least (n * num) >> shift, in 64 bits        */
+    uint32_t shift;              /* <= 31                                              */
+    uint32_t align;              /* capacity rounded up to a multiple: 1, 2, 4, .., 64 */
+} crdt_headroom;
+uint32_t crdt_headroom_capacity(const crdt_headroom* h /* NULL: packed */, uint32_t n);
+int crdt_replica_repack_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub /* or NULL */,
+                              const uint32_t* idx, const uint32_t* n_idx /* device, [1], or NULL */, uint32_t n_out,
+                              const crdt_headroom* entry_room, const crdt_headroom* tomb_room,
+                              uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out, void* stream);
 
 /* ---- delta merge of a resident replica pair ---------------------------------
  * (*AWSetDelta).Merge (awset-delta_test.go:51-65) applied to replicas in their
