@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/crdtgpu.h"
+#include "api_args.hpp"
 #include "crdt_device.hpp"
 #include "headroom.hpp"
 #include "replica.hpp"
@@ -353,44 +354,79 @@ SrcView view(const crdt_src_batch* s) {
                    s->actors,    s->counters, s->tomb_off, s->tkeys,     s->tactors, s->tcounters};
 }
 
-bool batch_ptrs_ok(const crdt_awset_batch* b) {
-    return b && b->offsets && (b->n_docs == 0 || b->vv) && b->R > 0 && b->R <= CRDT_MAX_R;
+TombView view(const crdt_tomb_batch* t) {  // NULL: no tombstones
+    return t ? TombView{t->offsets, t->counts, t->keys, t->actors, t->counters} : TombView{};
 }
 
-bool out_ptrs_ok(const crdt_awset_out* o) {
-    return o && o->offsets && o->counts && o->keys && o->actors && o->counters && o->vv;
+TombOut view(const crdt_tomb_out* t) {  // NULL: not written
+    return t ? TombOut{t->offsets, t->counts, t->keys, t->actors, t->counters} : TombOut{};
 }
 
-// crdt_diff_out against the two inputs (include/crdtgpu.h): required pointers,
-// the dots of a list both or neither, and no out array starting where an input
-// array of the same kind (or the other list's column) starts.
-bool diff_out_ok(const crdt_diff_out* o, const crdt_awset_batch* before, const crdt_awset_batch* after,
-                 uint32_t rem_slots, uint32_t ups_slots) {
-    if (!o || !o->flags || !o->rem_off || !o->ups_off) return false;
-    if ((rem_slots && !o->rem_keys) || (ups_slots && !o->ups_keys)) return false;
-    if ((o->rem_actors == nullptr) != (o->rem_counters == nullptr)) return false;
-    if ((o->ups_actors == nullptr) != (o->ups_counters == nullptr)) return false;
-    if (o->rem_off == o->ups_off) return false;
-    if (o->rem_keys && (o->rem_keys == o->ups_keys || o->rem_keys == o->rem_counters || o->rem_keys == o->ups_counters))
-        return false;
-    if (o->ups_keys && (o->ups_keys == o->rem_counters || o->ups_keys == o->ups_counters)) return false;
-    if (o->rem_actors && o->rem_actors == o->ups_actors) return false;
-    if (o->rem_counters && o->rem_counters == o->ups_counters) return false;
-    for (const crdt_awset_batch* b : {before, after}) {
-        for (const uint32_t* w : {(const uint32_t*)o->rem_off, (const uint32_t*)o->ups_off, (const uint32_t*)o->summary,
-                                  (const uint32_t*)o->rem_actors, (const uint32_t*)o->ups_actors})
-            if (w && (w == b->offsets || w == b->counts || w == b->actors)) return false;
-        for (const uint64_t* w : {(const uint64_t*)o->rem_keys, (const uint64_t*)o->ups_keys,
-                                  (const uint64_t*)o->rem_counters, (const uint64_t*)o->ups_counters})
-            if (w && (w == b->keys || w == b->counters || w == b->vv)) return false;
+MergeLogView view(const crdt_merge_log* l) {
+    return MergeLogView{l->flags,      l->summary,      l->rem_offsets, l->rem_counts, l->rem_keys,
+                        l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
+                        l->ups_actors, l->ups_counters, l->ups_kind};
+}
+
+DeltaOutView view(const crdt_delta_out* o, bool kind) {  // kind: the call writes out->kind
+    return DeltaOutView{o->doc_srcs, o->src_actor, o->vv,    o->entry_off, o->keys,      o->actors,
+                        o->counters, o->tomb_off,  o->tkeys, o->tactors,   o->tcounters, kind ? o->kind : nullptr};
+}
+
+HasView has_view(const crdt_awset_batch* b) {
+    return HasView{b->n_docs, b->offsets, b->counts, b->keys, b->actors, b->counters};
+}
+
+HasView has_view(const crdt_tomb_batch* t, uint32_t n_docs) {  // NULL: no tombstones
+    return t ? HasView{n_docs, t->offsets, t->counts, t->keys, t->actors, t->counters}
+             : HasView{n_docs, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+
+SrcCols cols(const crdt_awset_batch* b) { return SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters}; }
+
+SrcCols cols(const crdt_tomb_batch* t) {  // NULL: no tombstones
+    return t ? SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters} : SrcCols{};
+}
+
+PairSide pair_side(const crdt_awset_batch* st, const crdt_tomb_batch* t, const uint32_t* doc_actor, uint32_t actor) {
+    PairSide ps{};
+    ps.st = view(st);
+    ps.tb = view(t);
+    ps.doc_actor = doc_actor;
+    ps.actor = actor;
+    return ps;
+}
+
+RepSide rep_side(const crdt_replica* r) {
+    RepSide s{};
+    s.n_docs = r->state->n_docs;
+    s.actor = r->actor;
+    s.e = cols(r->state);
+    s.t = cols(r->tombs);
+    s.vv = r->state->vv;
+    s.doc_actor = r->doc_actor;
+    return s;
+}
+
+// One call that uses the context's shared workspace on a stream: the constructor
+// selects the device and enters (enter()), need() grows a workspace buffer, end()
+// leaves (leave()).  Every step is skipped once rc is an error; a return that
+// passes end() by records no event.
+struct Call {
+    crdt_ctx* ctx;
+    hipStream_t s;
+    bool cap = false;  // s is capturing a graph
+    int rc;
+    Call(crdt_ctx* c, void* stream) : ctx(c), s((hipStream_t)stream), rc(set_device(c)) {
+        if (rc == CRDT_OK) rc = enter(ctx, s, cap);
     }
-    return true;
-}
-
-bool src_ptrs_ok(const crdt_src_batch* s) {
-    return s && s->doc_srcs && s->src_actor && s->entry_off && s->R > 0 && s->R <= CRDT_MAX_R &&
-           (!s->tomb_off || (s->tkeys && s->tactors && s->tcounters));
-}
+    void need_bytes(DevBuf& b, size_t bytes) {
+        if (rc == CRDT_OK) rc = grow(b, bytes, cap);
+    }
+    void need(DevBuf& b, size_t words) { need_bytes(b, std::max<size_t>(words, 1) * sizeof(uint32_t)); }
+    int end(int launch_rc) { return leave(ctx, s, cap, launch_rc); }
+    int end(hipError_t e) { return end(hip_err(e)); }
+};
 
 }  // namespace
 
@@ -590,27 +626,21 @@ int crdt_ctx_sync(crdt_ctx* ctx, void* stream) {
 
 static int join_common(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_awset_batch* src,
                        const crdt_awset_out* out, const crdt_awset_out* out2, void* stream) {
-    if (!ctx || !batch_ptrs_ok(dst) || !batch_ptrs_ok(src) || !out_ptrs_ok(out) || (out2 && !out_ptrs_ok(out2)))
-        return CRDT_E_INVALID;
-    if (dst->n_docs != src->n_docs || dst->R != src->R) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(dst->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
+    if (!ctx || check_join(dst, src, out, out2) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, dst->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
     const bool no_large = ctx->max_doc_entries <= 64 || ctx->call_small;
     TileWork tw{};
     const bool tiles = !no_large && ctx->join_tiles;
     if (tiles) {
         const size_t n = std::max<size_t>(dst->n_docs, 1);
-        rc = grow(ctx->tile_desc, ((size_t)ctx->tile_cap + 1) * 16, cap);  // (+1: the next pass's first split)
-        if (rc == CRDT_OK) rc = grow(ctx->tile_geo, ((size_t)ctx->tile_cap + 8) * 32, cap);  // (+8: geo_slot)
-        if (rc == CRDT_OK) rc = grow(ctx->tile_flags, (size_t)ctx->tile_cap * 8, cap);
-        if (rc == CRDT_OK) rc = grow(ctx->tile_slot, n * 4, cap);
-        if (rc == CRDT_OK) rc = grow(ctx->tile_run, ((n + 1023) / 1024) * 4, cap);
-        if (rc != CRDT_OK) return rc;
+        c.need_bytes(ctx->tile_desc, ((size_t)ctx->tile_cap + 1) * 16);  // (+1: the next pass's first split)
+        c.need_bytes(ctx->tile_geo, ((size_t)ctx->tile_cap + 8) * 32);   // (+8: geo_slot)
+        c.need_bytes(ctx->tile_flags, (size_t)ctx->tile_cap * 8);
+        c.need_bytes(ctx->tile_slot, n * 4);
+        c.need_bytes(ctx->tile_run, ((n + 1023) / 1024) * 4);
+        if (c.rc != CRDT_OK) return c.rc;
         uint32_t* w = ctx->ws.as<uint32_t>(0);
         // Passes of tile_cap tiles: as many as the call's tiles can need.  A host-path
         // call counted them (ctx->call_tiles); otherwise a document of nd + ns merged
@@ -634,14 +664,13 @@ static int join_common(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_aw
                       ctx->tile_split_bpc, ctx->tile_shards, 0u, passes, passes_for(hard) <= passes ? 1u : 0u};
     }
     // the per-call counters are read only by the large-document paths
-    if (!no_large && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
+    if (!no_large && launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
     OutView o2v;
     if (out2) o2v = view(out2);
-    rc = hip_err(launch_join(view(dst), view(src), view(out), out2 ? &o2v : nullptr, make_work(ctx),
+    return c.end(launch_join(view(dst), view(src), view(out), out2 ? &o2v : nullptr, make_work(ctx),
                              ctx->join_docs_per_wave, ctx->join_nt_stores, ctx->join_stage_stores,
                              ctx->join_slab_per_cu * (uint32_t)ctx->n_cu, block_grid(ctx), no_large,
-                             tiles ? &tw : nullptr, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+                             tiles ? &tw : nullptr, (uint32_t)ctx->n_cu, c.s));
 }
 
 int crdt_awset_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_awset_batch* src,
@@ -651,60 +680,35 @@ int crdt_awset_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt
 
 int crdt_awset_exchange_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b,
                               const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, void* stream) {
-    // out_ba->keys == out_ab->keys: one shared key column (both directions hold
-    // the same keys at the same slots); every other array must be its own.
-    // Checked here: no two of the twelve arrays start at the same address
-    // (keys == keys excepted), and the per-document arrays, whose sizes the
-    // host knows (offsets, counts, vv), do not overlap at all.  The entry
-    // arrays' capacity lives in device memory, so a partial overlap of them
-    // cannot be checked and is undefined (include/crdtgpu.h).
-    if (!out_ab || !out_ba || !a) return CRDT_E_INVALID;
-    const size_t n = a->n_docs, R = a->R;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;  // 0: size unknown here (entry arrays)
-    };
-    const Range r[12] = {{(uintptr_t)out_ab->offsets, (n + 1) * 4}, {(uintptr_t)out_ab->counts, n * 4},
-                         {(uintptr_t)out_ab->vv, n * R * 8},       {(uintptr_t)out_ab->keys, 0},
-                         {(uintptr_t)out_ab->actors, 0},           {(uintptr_t)out_ab->counters, 0},
-                         {(uintptr_t)out_ba->offsets, (n + 1) * 4}, {(uintptr_t)out_ba->counts, n * 4},
-                         {(uintptr_t)out_ba->vv, n * R * 8},       {(uintptr_t)out_ba->keys, 0},
-                         {(uintptr_t)out_ba->actors, 0},           {(uintptr_t)out_ba->counters, 0}};
-    for (int i = 0; i < 12; ++i)
-        for (int j = i + 1; j < 12; ++j) {
-            if (i == 3 && j == 9) continue;  // the shared key column
-            if (!r[i].p || !r[j].p) continue;  // NULL pointers are rejected by join_common
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
-                return CRDT_E_INVALID;
-        }
+    if (check_exchange(a, b, out_ab, out_ba) != CRDT_OK) return CRDT_E_INVALID;
     return join_common(ctx, a, b, out_ab, out_ba, stream);
 }
 
-int crdt_awset_fold_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
-                          const crdt_awset_out* out, void* stream) {
-    if (!ctx || !batch_ptrs_ok(dst) || !src_ptrs_ok(srcs) || !out_ptrs_ok(out)) return CRDT_E_INVALID;
-    if (mode != CRDT_FOLD_AWSET && mode != CRDT_FOLD_DELTA) return CRDT_E_INVALID;
-    if (dst->n_docs != srcs->n_docs || dst->R != srcs->R) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(dst->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(dst->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
+// The fold's scratch copy of the output slots: at least one slot, never allocated
+// during a capture.
+static int fold_scratch(crdt_ctx* ctx, bool cap, Scratch* scr) {
     if (ctx->scratch_slots == 0) {
         if (cap) return CRDT_E_WORKSPACE;
         if (reserve_scratch(ctx, 1) != CRDT_OK) return CRDT_E_NOMEM;
     }
-    if (launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
     const size_t slots = ctx->scratch_slots;
-    Scratch scr{ctx->scratch.as<uint64_t>(0), ctx->scratch.as<uint32_t>(slots * 16), ctx->scratch.as<uint64_t>(slots * 8),
-                slots};
-    rc = hip_err(launch_fold(mode, view(dst), view(srcs), view(out), scr, make_work(ctx), block_grid(ctx),
-                             ctx->fold_lean_first, s));
-    return leave(ctx, s, cap, rc);
+    *scr = Scratch{ctx->scratch.as<uint64_t>(0), ctx->scratch.as<uint32_t>(slots * 16),
+                   ctx->scratch.as<uint64_t>(slots * 8), slots};
+    return CRDT_OK;
+}
+
+int crdt_awset_fold_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
+                          const crdt_awset_out* out, void* stream) {
+    if (!ctx || check_fold(mode, dst, srcs, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, dst->n_docs);
+    c.need(ctx->defer, dst->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    Scratch scr;
+    if (int rc = fold_scratch(ctx, c.cap, &scr)) return rc;
+    if (launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
+    return c.end(launch_fold(mode, view(dst), view(srcs), view(out), scr, make_work(ctx), block_grid(ctx),
+                             ctx->fold_lean_first, c.s));
 }
 
 // The group counts of the extraction (extract.hip) live in the worklist and
@@ -712,60 +716,39 @@ int crdt_awset_fold_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, 
 // which is what crdt_ctx_reserve(max_docs, ..) sizes them for.
 int crdt_awset_delta_extract_async(crdt_ctx* ctx, const crdt_src_batch* srcs, const uint64_t* peer_vv,
                                    const crdt_delta_out* out, void* stream) {
-    if (!ctx || !src_ptrs_ok(srcs) || !out || (srcs->n_docs && !peer_vv)) return CRDT_E_INVALID;
-    if (!out->doc_srcs || !out->src_actor || !out->vv || !out->entry_off || !out->keys || !out->actors ||
-        !out->counters)
-        return CRDT_E_INVALID;
-    if (srcs->tomb_off && (!out->tomb_off || !out->tkeys || !out->tactors || !out->tcounters)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(srcs->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(srcs->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
-    const DeltaOutView ov{out->doc_srcs, out->src_actor, out->vv,    out->entry_off, out->keys,      out->actors,
-                          out->counters, out->tomb_off,  out->tkeys, out->tactors,   out->tcounters, out->kind};
-    rc = hip_err(launch_extract(view(srcs), peer_vv, ov, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(),
-                                make_work(ctx), (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    if (!ctx || check_extract(srcs, peer_vv, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, srcs->n_docs);
+    c.need(ctx->defer, srcs->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_extract(view(srcs), peer_vv, view(out, true), ctx->worklist.as<uint32_t>(),
+                                ctx->defer.as<uint32_t>(), make_work(ctx), (uint32_t)ctx->n_cu, c.s));
 }
 
 // Membership reads (query.hip): one launch over the five-array view, ordered
 // after the context's previous call like every call that shares its status word.
 static int has_common(crdt_ctx* ctx, const HasView& sv, const crdt_query_batch* q, const crdt_query_out* out,
                       void* stream) {
-    if (!q->q_off || !out->found || (q->n_queries && !q->keys) || q->n_docs != sv.n_docs ||
-        (out->actors == nullptr) != (out->counters == nullptr))
-        return CRDT_E_INVALID;
     if (q->n_queries == 0) return CRDT_OK;
     if (sv.n_docs == 0) return CRDT_E_INVALID;  // (queries of no document)
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
     const Work wk = make_work(ctx);
-    rc = hip_err(launch_has(sv, HasQueries{q->n_queries, q->q_off, q->keys},
-                            HasOut{out->found, out->actors, out->counters}, wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_has(sv, HasQueries{q->n_queries, q->q_off, q->keys},
+                            HasOut{out->found, out->actors, out->counters}, wk.status, wk.gate, (uint32_t)ctx->n_cu,
+                            c.s));
 }
 
 int crdt_awset_has_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_query_batch* q,
                          const crdt_query_out* out, void* stream) {
-    if (!ctx || !state || !q || !out || !state->offsets || state->R == 0 || state->R > CRDT_MAX_R)
-        return CRDT_E_INVALID;
-    return has_common(ctx, HasView{state->n_docs, state->offsets, state->counts, state->keys, state->actors,
-                                   state->counters}, q, out, stream);
+    if (!ctx || check_has(state, q, out) != CRDT_OK) return CRDT_E_INVALID;
+    return has_common(ctx, has_view(state), q, out, stream);
 }
 
 int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_docs, const crdt_query_batch* q,
                         const crdt_query_out* out, void* stream) {
-    if (!ctx || !tombs || !q || !out || !tombs->offsets) return CRDT_E_INVALID;
-    return has_common(ctx, HasView{n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors,
-                                   tombs->counters}, q, out, stream);
+    if (!ctx || check_tomb_has(tombs, n_docs, q, out) != CRDT_OK) return CRDT_E_INVALID;
+    return has_common(ctx, has_view(tombs, n_docs), q, out, stream);
 }
 
 // Convergence check (compare.hip).  The per-document flag words the entry and
@@ -773,85 +756,48 @@ int crdt_tomb_has_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_t n_
 // what crdt_ctx_reserve(max_docs, ..) sizes it for.
 int crdt_awset_compare_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
                              const crdt_compare_out* out, void* stream) {
-    if (!ctx || !batch_ptrs_ok(a) || !batch_ptrs_ok(b) || !out || !out->flags) return CRDT_E_INVALID;
-    if (a->n_docs != b->n_docs || a->R != b->R || mask > 15u) return CRDT_E_INVALID;
-    if ((out->worklist == nullptr) != (out->n_work == nullptr)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
+    if (!ctx || check_compare(a, b, mask, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->defer, a->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
     const Work wk = make_work(ctx);
-    rc = hip_err(launch_compare(view(a), view(b), mask,
+    return c.end(launch_compare(view(a), view(b), mask,
                                 CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
-                                ctx->defer.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+                                ctx->defer.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, c.s));
 }
 
 // State digests (digest.hip): the digest words are the accumulators, no workspace.
 int crdt_awset_digest_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
                             uint64_t* digest, void* stream) {
-    if (!ctx || !batch_ptrs_ok(state) || !digest || (tombs && !tombs->offsets)) return CRDT_E_INVALID;
-    for (const void* p : {(const void*)state->offsets, (const void*)state->counts, (const void*)state->keys,
-                          (const void*)state->actors, (const void*)state->counters, (const void*)state->vv})
-        if (p == digest) return CRDT_E_INVALID;
-    if (tombs)
-        for (const void* p : {(const void*)tombs->offsets, (const void*)tombs->counts, (const void*)tombs->keys,
-                              (const void*)tombs->actors, (const void*)tombs->counters})
-            if (p == digest) return CRDT_E_INVALID;
+    if (!ctx || check_digest(state, tombs, digest) != CRDT_OK) return CRDT_E_INVALID;
     if (state->n_docs == 0) return CRDT_OK;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
-    const HasView sv{state->n_docs, state->offsets, state->counts, state->keys, state->actors, state->counters};
-    const HasView tv = tombs ? HasView{state->n_docs, tombs->offsets, tombs->counts, tombs->keys, tombs->actors,
-                                       tombs->counters}
-                             : HasView{state->n_docs, nullptr, nullptr, nullptr, nullptr, nullptr};
-    rc = hip_err(launch_digest(sv, tv, state->vv, state->R, digest, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest(has_view(state), has_view(tombs, state->n_docs), state->vv, state->R, digest,
+                               make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
 }
 
 // Digest comparison (digest.hip, then compare.hip's worklist step): the flag
 // words live in the defer buffer, one per document, as in the compare.
 int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* theirs, uint32_t n_docs, uint32_t mask,
                            const crdt_compare_out* out, void* stream) {
-    if (!ctx || !out || !out->flags || mask > 15u) return CRDT_E_INVALID;
-    if (n_docs && (!mine || !theirs)) return CRDT_E_INVALID;
-    if ((out->worklist == nullptr) != (out->n_work == nullptr)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_digest_diff(mine, theirs, n_docs, mask,
+    if (!ctx || check_digest_diff(mine, theirs, n_docs, mask, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->defer, n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest_diff(mine, theirs, n_docs, mask,
                                     CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
-                                    ctx->defer.as<uint32_t>(), make_work(ctx).gate, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+                                    ctx->defer.as<uint32_t>(), make_work(ctx).gate, (uint32_t)ctx->n_cu, c.s));
 }
 
 // Sub-batch selection / compaction (compare.hip): no workspace.
 int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const uint32_t* idx, const uint32_t* n_idx,
                             uint32_t n_out, uint32_t out_slots, const crdt_awset_out* out, void* stream) {
-    if (!ctx || !batch_ptrs_ok(state) || !out_ptrs_ok(out)) return CRDT_E_INVALID;
-    if (out->offsets == state->offsets || out->counts == state->counts || out->keys == state->keys ||
-        out->actors == state->actors || out->counters == state->counters || out->vv == state->vv)
-        return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_select(view(state), idx, n_idx, n_out, out_slots, view(out), make_work(ctx).status,
-                               (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    if (!ctx || check_select(state, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_select(view(state), idx, n_idx, n_out, out_slots, view(out), make_work(ctx).status,
+                               (uint32_t)ctx->n_cu, c.s));
 }
 
 // Scatter (scatter.hip): the inverse map (one word per state document) lives in
@@ -861,23 +807,13 @@ int crdt_awset_select_async(crdt_ctx* ctx, const crdt_awset_batch* state, const 
 int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_awset_batch* sub,
                              const uint32_t* idx, const uint32_t* n_idx, uint32_t out_slots, const crdt_awset_out* out,
                              void* stream) {
-    if (!ctx || !batch_ptrs_ok(state) || !batch_ptrs_ok(sub) || !idx || !out_ptrs_ok(out)) return CRDT_E_INVALID;
-    if (state->R != sub->R) return CRDT_E_INVALID;
-    for (const crdt_awset_batch* b : {state, sub})
-        if (out->offsets == b->offsets || out->counts == b->counts || out->keys == b->keys ||
-            out->actors == b->actors || out->counters == b->counters || out->vv == b->vv)
-            return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(state->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(state->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_scatter(view(state), view(sub), idx, n_idx, out_slots, view(out), ctx->worklist.as<uint32_t>(),
-                                ctx->defer.as<uint32_t>(), make_work(ctx).status, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    if (!ctx || check_scatter(state, sub, idx, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, state->n_docs);
+    c.need(ctx->defer, state->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_scatter(view(state), view(sub), idx, n_idx, out_slots, view(out), ctx->worklist.as<uint32_t>(),
+                                ctx->defer.as<uint32_t>(), make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
 }
 
 // Merge diff (diff.hip): the per-document flag words the count pass ORs into live
@@ -887,23 +823,16 @@ int crdt_awset_scatter_async(crdt_ctx* ctx, const crdt_awset_batch* state, const
 // buffer, allocated once at crdt_ctx_create.
 int crdt_awset_diff_async(crdt_ctx* ctx, const crdt_awset_batch* before, const crdt_awset_batch* after,
                           uint32_t rem_slots, uint32_t ups_slots, const crdt_diff_out* out, void* stream) {
-    if (!ctx || !batch_ptrs_ok(before) || !batch_ptrs_ok(after)) return CRDT_E_INVALID;
-    if (before->n_docs != after->n_docs || before->R != after->R) return CRDT_E_INVALID;
-    if (!diff_out_ok(out, before, after, rem_slots, ups_slots)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(before->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK && ctx->parts.bytes < diff_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
-    if (rc != CRDT_OK) return rc;
+    if (!ctx || check_diff(before, after, rem_slots, ups_slots, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->defer, before->n_docs);
+    if (c.rc == CRDT_OK && ctx->parts.bytes < diff_parts_bytes()) c.rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (c.rc != CRDT_OK) return c.rc;
     const Work wk = make_work(ctx);
     const DiffOutView ov{out->flags,      out->summary,  out->rem_off,    out->rem_keys,     out->rem_actors, out->rem_counters,
                          out->ups_off,    out->ups_keys, out->ups_actors, out->ups_counters, out->ups_kind};
-    rc = hip_err(launch_diff(view(before), view(after), rem_slots, ups_slots, ov, ctx->defer.as<uint32_t>(),
-                             ctx->parts.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_diff(view(before), view(after), rem_slots, ups_slots, ov, ctx->defer.as<uint32_t>(),
+                             ctx->parts.as<uint32_t>(), wk.status, wk.gate, (uint32_t)ctx->n_cu, c.s));
 }
 
 // Sources (sources.hip): the scan's partial sums, one word per 1,024 sources for
@@ -911,54 +840,30 @@ int crdt_awset_diff_async(crdt_ctx* ctx, const crdt_awset_batch* before, const c
 // replica descriptors are flattened into the kernel arguments here.
 int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n_reps, uint32_t entry_slots,
                              uint32_t tomb_slots, const crdt_delta_out* out, void* stream) {
-    if (!ctx || !reps || !out || n_reps == 0 || n_reps > CRDT_MAX_REPLICAS) return CRDT_E_INVALID;
-    if (!out->doc_srcs || !out->src_actor || !out->vv || !out->entry_off || !out->keys || !out->actors ||
-        !out->counters)
-        return CRDT_E_INVALID;
+    if (!ctx || check_sources(reps, n_reps, out) != CRDT_OK) return CRDT_E_INVALID;
     SourcesArgs a{};
     for (uint32_t p = 0; p < n_reps; ++p) {
-        const crdt_awset_batch* b = reps[p].state;
-        if (!batch_ptrs_ok(b)) return CRDT_E_INVALID;
-        if (b->n_docs != reps[0].state->n_docs || b->R != reps[0].state->R) return CRDT_E_INVALID;
-        if (out->entry_off == b->offsets || out->keys == b->keys || out->actors == b->actors ||
-            out->counters == b->counters || out->vv == b->vv || (out->src_actor && out->src_actor == reps[p].doc_actor))
-            return CRDT_E_INVALID;
         SrcRep& r = a.rep[p];
-        r.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
-        r.vv = b->vv;
+        r.e = cols(reps[p].state);
+        r.t = cols(reps[p].tombs);
+        r.vv = reps[p].state->vv;
         r.doc_actor = reps[p].doc_actor;
         r.actor = reps[p].actor;
-        if (const crdt_tomb_batch* t = reps[p].tombs) {
-            if (!t->offsets) return CRDT_E_INVALID;
-            if (!out->tomb_off || !out->tkeys || !out->tactors || !out->tcounters) return CRDT_E_INVALID;
-            if (out->tomb_off == t->offsets || out->tkeys == t->keys || out->tactors == t->actors ||
-                out->tcounters == t->counters)
-                return CRDT_E_INVALID;
-            r.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
-        }
     }
-    const uint64_t n_srcs = (uint64_t)reps[0].state->n_docs * n_reps;
-    if (n_srcs >= (1ull << 32)) return CRDT_E_INVALID;
     a.n_reps = n_reps;
     a.n_docs = reps[0].state->n_docs;
     a.R = reps[0].state->R;
-    a.n_srcs = (uint32_t)n_srcs;
+    a.n_srcs = a.n_docs * n_reps;  // (< 2^32: checked)
     a.entry_slots = entry_slots;
     a.tomb_slots = tomb_slots;
-    a.out = DeltaOutView{out->doc_srcs, out->src_actor, out->vv,    out->entry_off, out->keys,      out->actors,
-                         out->counters, out->tomb_off,  out->tkeys, out->tactors,   out->tcounters, nullptr};
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    const size_t n_parts = (size_t)((n_srcs + 1023) / 1024);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_sources(a, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(), make_work(ctx).status,
-                                (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    a.out = view(out, false);
+    Call c(ctx, stream);
+    const size_t n_parts = ((size_t)a.n_srcs + 1023) / 1024;
+    c.need(ctx->worklist, n_parts);
+    c.need(ctx->defer, n_parts);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_sources(a, ctx->worklist.as<uint32_t>(), ctx->defer.as<uint32_t>(), make_work(ctx).status,
+                                (uint32_t)ctx->n_cu, c.s));
 }
 
 // Replica select / scatter (replica.hip).  sub == NULL: the select.  The scan's
@@ -968,56 +873,15 @@ int crdt_awset_sources_async(crdt_ctx* ctx, const crdt_replica* reps, uint32_t n
 // and both partial arrays in the defer buffer (2 * ceil(n / 1,024) <= max(n, 2)
 // words), which is what crdt_ctx_reserve(max_docs, ..) sizes them for.
 // room != NULL: the repack (replica_repack.hip) with the entry policy room[0] and
-// the tombstone policy room[1]; same arguments, checks and workspace.
+// the tombstone policy room[1]; same arguments and workspace.  The callers have
+// checked the arguments.
 static int replica_common(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
                           const uint32_t* n_idx, uint32_t n_out, uint32_t entry_slots, uint32_t tomb_slots,
                           const crdt_replica_out* out, bool scatter, void* stream,
                           const crdt_headroom* room = nullptr) {
-    if (!ctx || !rep || !batch_ptrs_ok(rep->state) || !out || !out_ptrs_ok(out->state)) return CRDT_E_INVALID;
-    if (scatter && (!sub || !batch_ptrs_ok(sub->state) || !idx || sub->state->R != rep->state->R))
-        return CRDT_E_INVALID;
-    const crdt_replica* in[2] = {rep, scatter ? sub : nullptr};
-    const crdt_awset_out* os = out->state;
-    const crdt_tomb_out* ot = out->tombs;
-    bool any_t = false;
-    for (const crdt_replica* r : in) {
-        if (!r) continue;
-        const crdt_awset_batch* b = r->state;
-        const crdt_tomb_batch* t = r->tombs;
-        if (t) {
-            if (!t->offsets) return CRDT_E_INVALID;
-            any_t = true;
-        }
-        // no output array starts where an input array of the same kind starts
-        const uint32_t* in32[] = {b->offsets, b->counts, b->actors, r->doc_actor, t ? t->offsets : nullptr,
-                                  t ? t->counts : nullptr, t ? t->actors : nullptr};
-        const uint64_t* in64[] = {b->keys, b->counters, b->vv, t ? t->keys : nullptr, t ? t->counters : nullptr};
-        const uint32_t* out32[] = {os->offsets, os->counts, os->actors, out->doc_actor, ot ? ot->offsets : nullptr,
-                                   ot ? ot->counts : nullptr, ot ? ot->actors : nullptr};
-        const uint64_t* out64[] = {os->keys, os->counters, os->vv, ot ? ot->keys : nullptr, ot ? ot->counters : nullptr};
-        for (const uint32_t* o : out32)
-            for (const uint32_t* i : in32)
-                if (o && o == i) return CRDT_E_INVALID;
-        for (const uint64_t* o : out64)
-            for (const uint64_t* i : in64)
-                if (o && o == i) return CRDT_E_INVALID;
-    }
-    if (any_t && (!ot || !ot->offsets || !ot->counts || !ot->keys || !ot->actors || !ot->counters))
-        return CRDT_E_INVALID;
-    auto side = [](const crdt_replica* r) {
-        RepSide s{};
-        const crdt_awset_batch* b = r->state;
-        s.n_docs = b->n_docs;
-        s.actor = r->actor;
-        s.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
-        if (const crdt_tomb_batch* t = r->tombs) s.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
-        s.vv = b->vv;
-        s.doc_actor = r->doc_actor;
-        return s;
-    };
     ReplicaArgs a{};
-    a.rep = side(rep);
-    if (scatter) a.sub = side(sub);
+    a.rep = rep_side(rep);
+    if (scatter) a.sub = rep_side(sub);
     a.idx = idx;
     a.n_idx = n_idx;
     // an empty call writes offsets[0] = 0 alone and launches nothing that reads documents
@@ -1026,51 +890,46 @@ static int replica_common(crdt_ctx* ctx, const crdt_replica* rep, const crdt_rep
     a.R = rep->state->R;
     a.entry_slots = entry_slots;
     a.tomb_slots = tomb_slots;
-    a.out = view(os);
-    if (ot) {
-        a.tout = TombOut{ot->offsets, ot->counts, ot->keys, ot->actors, ot->counters};
-        if (!any_t) a.tout.keys = nullptr;  // offsets (and counts) zeroed, no column written
-    }
+    a.out = view(out->state);
+    a.tout = view(out->tombs);
+    // no input has tombstones: offsets (and counts) zeroed, no column written
+    if (!rep->tombs && !(scatter && sub->tombs)) a.tout.keys = nullptr;
     a.out_actor = out->doc_actor;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
+    Call c(ctx, stream);
     const size_t n_parts = ((size_t)n + 1023) / 1024;
     uint32_t *inv = nullptr, *parts_e = nullptr, *parts_t = nullptr;
     if (scatter) {
-        if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n, 1) * sizeof(uint32_t), cap);
-        if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(2 * n_parts, 2) * sizeof(uint32_t), cap);
-        if (rc != CRDT_OK) return rc;
+        c.need(ctx->worklist, n);
+        c.need(ctx->defer, std::max<size_t>(2 * n_parts, 2));
+        if (c.rc != CRDT_OK) return c.rc;
         inv = ctx->worklist.as<uint32_t>();
         parts_e = ctx->defer.as<uint32_t>();
         parts_t = parts_e + n_parts;
         a.inv = inv;
     } else {
-        if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
-        if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_parts, 1) * sizeof(uint32_t), cap);
-        if (rc != CRDT_OK) return rc;
+        c.need(ctx->worklist, n_parts);
+        c.need(ctx->defer, n_parts);
+        if (c.rc != CRDT_OK) return c.rc;
         parts_e = ctx->worklist.as<uint32_t>();
         parts_t = ctx->defer.as<uint32_t>();
     }
     if (room)
-        rc = hip_err(launch_replica_repack(RepackArgs{a, room[0], room[1]}, inv, parts_e, parts_t,
-                                           make_work(ctx).status, (uint32_t)ctx->n_cu, s));
-    else
-        rc = hip_err(launch_replica(a, inv, parts_e, parts_t, make_work(ctx).status, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+        return c.end(launch_replica_repack(RepackArgs{a, room[0], room[1]}, inv, parts_e, parts_t,
+                                           make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
+    return c.end(launch_replica(a, inv, parts_e, parts_t, make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
 }
 
 int crdt_replica_select_async(crdt_ctx* ctx, const crdt_replica* rep, const uint32_t* idx, const uint32_t* n_idx,
                               uint32_t n_out, uint32_t entry_slots, uint32_t tomb_slots, const crdt_replica_out* out,
                               void* stream) {
+    if (!ctx || check_replica(rep, nullptr, idx, out, false) != CRDT_OK) return CRDT_E_INVALID;
     return replica_common(ctx, rep, nullptr, idx, n_idx, n_out, entry_slots, tomb_slots, out, false, stream);
 }
 
 int crdt_replica_scatter_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt_replica* sub, const uint32_t* idx,
                                const uint32_t* n_idx, uint32_t entry_slots, uint32_t tomb_slots,
                                const crdt_replica_out* out, void* stream) {
+    if (!ctx || check_replica(rep, sub, idx, out, true) != CRDT_OK) return CRDT_E_INVALID;
     return replica_common(ctx, rep, sub, idx, n_idx, 0u, entry_slots, tomb_slots, out, true, stream);
 }
 
@@ -1089,7 +948,7 @@ int crdt_replica_repack_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt
                               const crdt_replica_out* out, void* stream) {
     const crdt_headroom room[2] = {entry_room ? *entry_room : kHeadroomPacked, tomb_room ? *tomb_room : kHeadroomPacked};
     if (!headroom_ok(room[0]) || !headroom_ok(room[1])) return CRDT_E_INVALID;
-    if (sub && (!rep || !rep->state || n_out != rep->state->n_docs)) return CRDT_E_INVALID;
+    if (!ctx || check_replica_repack(rep, sub, idx, n_out, out) != CRDT_OK) return CRDT_E_INVALID;
     return replica_common(ctx, rep, sub, idx, n_idx, n_out, entry_slots, tomb_slots, out, sub != nullptr, stream, room);
 }
 
@@ -1101,36 +960,9 @@ int crdt_replica_repack_async(crdt_ctx* ctx, const crdt_replica* rep, const crdt
 int crdt_replica_scatter_inplace_async(crdt_ctx* ctx, const crdt_replica_inplace* rep, const crdt_replica* sub,
                                        const uint32_t* idx, const uint32_t* n_idx, const crdt_spill_out* spill,
                                        void* stream) {
-    if (!ctx || !rep || !sub || !batch_ptrs_ok(sub->state) || !idx || !spill) return CRDT_E_INVALID;
-    if (!spill->spill_j || !spill->spill_doc || !spill->n_spill) return CRDT_E_INVALID;
-    if (!rep->offsets || !rep->counts || !rep->keys || !rep->actors || !rep->counters || !rep->vv)
-        return CRDT_E_INVALID;
-    if (rep->R != sub->state->R || rep->R == 0 || rep->R > CRDT_MAX_R) return CRDT_E_INVALID;
-    const crdt_awset_batch* b = sub->state;
-    const crdt_tomb_batch* t = sub->tombs;
-    if (t && (!t->offsets || !rep->tomb_offsets || !rep->tkeys || !rep->tactors || !rep->tcounters))
-        return CRDT_E_INVALID;
-    if (rep->tomb_offsets && !rep->tomb_counts) return CRDT_E_INVALID;
-    // no written array of rep starts where an array of the same kind of sub starts
-    const uint32_t* in32[] = {b->offsets, b->counts, b->actors, sub->doc_actor, t ? t->offsets : nullptr,
-                              t ? t->counts : nullptr, t ? t->actors : nullptr};
-    const uint64_t* in64[] = {b->keys, b->counters, b->vv, t ? t->keys : nullptr, t ? t->counters : nullptr};
-    const uint32_t* out32[] = {rep->counts, rep->actors, rep->tomb_counts, rep->tactors, rep->doc_actor,
-                               spill->spill_j, spill->spill_doc, spill->n_spill};
-    const uint64_t* out64[] = {rep->keys, rep->counters, rep->vv, rep->tkeys, rep->tcounters};
-    for (const uint32_t* o : out32)
-        for (const uint32_t* i : in32)
-            if (o && o == i) return CRDT_E_INVALID;
-    for (const uint64_t* o : out64)
-        for (const uint64_t* i : in64)
-            if (o && o == i) return CRDT_E_INVALID;
+    if (!ctx || check_inplace(rep, sub, idx, spill) != CRDT_OK) return CRDT_E_INVALID;
     InplaceArgs a{};
-    a.sub.n_docs = b->n_docs;
-    a.sub.actor = sub->actor;
-    a.sub.e = SrcCols{b->offsets, b->counts, b->keys, b->actors, b->counters};
-    if (t) a.sub.t = SrcCols{t->offsets, t->counts, t->keys, t->actors, t->counters};
-    a.sub.vv = b->vv;
-    a.sub.doc_actor = sub->doc_actor;
+    a.sub = rep_side(sub);
     a.n_docs = rep->n_docs;
     a.R = rep->R;
     a.e = InplaceCols{rep->offsets, rep->counts, rep->keys, rep->actors, rep->counters};
@@ -1143,113 +975,49 @@ int crdt_replica_scatter_inplace_async(crdt_ctx* ctx, const crdt_replica_inplace
     a.spill_j = spill->spill_j;
     a.spill_doc = spill->spill_doc;
     a.n_spill = spill->n_spill;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    const size_t n_sub = b->n_docs;
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(rep->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->defer, std::max<size_t>(n_sub, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->spill_parts, (n_sub / 1024 + 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
+    Call c(ctx, stream);
+    const size_t n_sub = sub->state->n_docs;
+    c.need(ctx->worklist, rep->n_docs);
+    c.need(ctx->defer, n_sub);
+    c.need_bytes(ctx->spill_parts, (n_sub / 1024 + 1) * sizeof(uint32_t));
+    if (c.rc != CRDT_OK) return c.rc;
     a.verdict = ctx->defer.as<uint32_t>();
-    rc = hip_err(launch_replica_inplace(a, ctx->worklist.as<uint32_t>(), ctx->spill_parts.as<uint32_t>(),
-                                        make_work(ctx).status, (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_replica_inplace(a, ctx->worklist.as<uint32_t>(), ctx->spill_parts.as<uint32_t>(),
+                                        make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
 }
 
 // Delta merge of a resident pair (delta_pair.hip).  Workspace: the join's
 // worklist, one word per document, which crdt_ctx_reserve(max_docs, ..) sizes.
 // a_tombs / a_doc_actor / a_actor: replica a beyond its state (the exchange);
-// out_ba == NULL: the join, which reads none of them.
+// out_ba == NULL: the join, which reads none of them.  The callers have checked
+// the arguments.
 static int delta_pair_common(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_tomb_batch* a_tombs,
                              const uint32_t* a_doc_actor, uint32_t a_actor, const crdt_replica* b,
                              const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
                              uint8_t* kind_ba, void* stream) {
-    if (!ctx || !batch_ptrs_ok(a) || !b || !batch_ptrs_ok(b->state) || !out_ptrs_ok(out_ab) ||
-        (out_ba && !out_ptrs_ok(out_ba)))
-        return CRDT_E_INVALID;
-    const crdt_awset_batch* bs = b->state;
-    if (a->n_docs != bs->n_docs || a->R != bs->R) return CRDT_E_INVALID;
-    if ((a_tombs && !a_tombs->offsets) || (b->tombs && !b->tombs->offsets)) return CRDT_E_INVALID;
-    // No two output arrays start at one address (the two directions keep different
-    // keys: there is no shared key column), the per-document arrays, whose sizes
-    // the host knows, do not overlap at all, and no output array starts where an
-    // input array of the same kind starts.
-    const size_t n = a->n_docs, R = a->R;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;  // 0: size unknown here (entry arrays)
-    };
-    Range r[12];
-    int nr = 0;
-    for (const crdt_awset_out* o : {out_ab, out_ba}) {
-        if (!o) continue;
-        r[nr++] = {(uintptr_t)o->offsets, (n + 1) * 4};
-        r[nr++] = {(uintptr_t)o->counts, n * 4};
-        r[nr++] = {(uintptr_t)o->vv, n * R * 8};
-        r[nr++] = {(uintptr_t)o->keys, 0};
-        r[nr++] = {(uintptr_t)o->actors, 0};
-        r[nr++] = {(uintptr_t)o->counters, 0};
-    }
-    for (int i = 0; i < nr; ++i)
-        for (int j = i + 1; j < nr; ++j) {
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
-                return CRDT_E_INVALID;
-        }
-    if (kind_ab && kind_ab == kind_ba) return CRDT_E_INVALID;
-    const crdt_tomb_batch* tb[2] = {a_tombs, b->tombs};
-    const crdt_awset_batch* st[2] = {a, bs};
-    const uint32_t* da[2] = {a_doc_actor, b->doc_actor};
-    for (const crdt_awset_out* o : {out_ab, out_ba}) {
-        if (!o) continue;
-        for (int p = 0; p < 2; ++p) {
-            for (const uint32_t* w : {(const uint32_t*)o->offsets, (const uint32_t*)o->counts, (const uint32_t*)o->actors}) {
-                if (w == st[p]->offsets || w == st[p]->counts || w == st[p]->actors || w == da[p]) return CRDT_E_INVALID;
-                if (tb[p] && (w == tb[p]->offsets || w == tb[p]->counts || w == tb[p]->actors)) return CRDT_E_INVALID;
-            }
-            for (const uint64_t* w : {(const uint64_t*)o->keys, (const uint64_t*)o->counters, (const uint64_t*)o->vv}) {
-                if (w == st[p]->keys || w == st[p]->counters || w == st[p]->vv) return CRDT_E_INVALID;
-                if (tb[p] && (w == tb[p]->keys || w == tb[p]->counters)) return CRDT_E_INVALID;
-            }
-        }
-    }
+    if (!ctx) return CRDT_E_INVALID;
     if (a->n_docs == 0) return CRDT_OK;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc != CRDT_OK) return rc;
-    if (launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
-    auto side = [](const crdt_awset_batch* st_, const crdt_tomb_batch* t, const uint32_t* doc_actor, uint32_t actor) {
-        PairSide ps{};
-        ps.st = view(st_);
-        if (t) ps.tb = TombView{t->offsets, t->counts, t->keys, t->actors, t->counters};
-        ps.doc_actor = doc_actor;
-        ps.actor = actor;
-        return ps;
-    };
+    Call c(ctx, stream);
+    c.need(ctx->worklist, a->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    if (launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
     OutView o2v;
     if (out_ba) o2v = view(out_ba);
-    rc = hip_err(launch_delta_pair(side(a, a_tombs, a_doc_actor, a_actor), side(bs, b->tombs, b->doc_actor, b->actor),
-                                   view(out_ab), out_ba ? &o2v : nullptr, kind_ab, kind_ba, make_work(ctx),
-                                   block_grid(ctx), s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_delta_pair(pair_side(a, a_tombs, a_doc_actor, a_actor),
+                                   pair_side(b->state, b->tombs, b->doc_actor, b->actor), view(out_ab),
+                                   out_ba ? &o2v : nullptr, kind_ab, kind_ba, make_work(ctx), block_grid(ctx), c.s));
 }
 
 int crdt_awset_delta_join_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
                                 const crdt_awset_out* out, uint8_t* kind, void* stream) {
+    if (check_delta_pair(dst, nullptr, nullptr, src, out, nullptr, kind, nullptr) != CRDT_OK) return CRDT_E_INVALID;
     return delta_pair_common(ctx, dst, nullptr, nullptr, 0u, src, out, nullptr, kind, nullptr, stream);
 }
 
 int crdt_awset_delta_exchange_async(crdt_ctx* ctx, const crdt_replica* a, const crdt_replica* b,
                                     const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
                                     uint8_t* kind_ba, void* stream) {
-    if (!a || !out_ba) return CRDT_E_INVALID;
+    if (check_delta_exchange(a, b, out_ab, out_ba, kind_ab, kind_ba) != CRDT_OK) return CRDT_E_INVALID;
     return delta_pair_common(ctx, a->state, a->tombs, a->doc_actor, a->actor, b, out_ab, out_ba, kind_ab, kind_ba,
                              stream);
 }
@@ -1260,231 +1028,70 @@ int crdt_awset_delta_exchange_async(crdt_ctx* ctx, const crdt_replica* a, const 
 // out_ba / log_ba == NULL: the join.
 static int join_log_common(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b,
                            const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, const crdt_merge_log* log_ab,
-                           const crdt_merge_log* log_ba, void* stream) {
-    if (!ctx || !batch_ptrs_ok(a) || !batch_ptrs_ok(b) || !out_ptrs_ok(out_ab) || (out_ba && !out_ptrs_ok(out_ba)))
-        return CRDT_E_INVALID;
-    if (a->n_docs != b->n_docs || a->R != b->R) return CRDT_E_INVALID;
-    const crdt_merge_log* const logs[2] = {log_ab, log_ba};
-    const int n_logs = out_ba ? 2 : 1;
-    for (int i = 0; i < n_logs; ++i) {
-        const crdt_merge_log* l = logs[i];
-        if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
-            !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
-            return CRDT_E_INVALID;
-    }
-    // No two written arrays start at one address (the shared key column of the
-    // plain exchange included), the per-document arrays, whose sizes the host
-    // knows, do not overlap at all, and no written array starts where an input
-    // array of the same kind starts.
-    const size_t n = a->n_docs, R = a->R;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;  // 0: size unknown here (entry arrays)
-        int width;     // bytes per element: the array's kind
-    };
-    std::vector<Range> r;
-    for (const crdt_awset_out* o : {out_ab, out_ba}) {
-        if (!o) continue;
-        r.push_back({(uintptr_t)o->offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)o->counts, n * 4, 4});
-        r.push_back({(uintptr_t)o->vv, n * R * 8, 8});
-        r.push_back({(uintptr_t)o->keys, 0, 8});
-        r.push_back({(uintptr_t)o->actors, 0, 4});
-        r.push_back({(uintptr_t)o->counters, 0, 8});
-    }
-    for (int i = 0; i < n_logs; ++i) {
-        const crdt_merge_log* l = logs[i];
-        r.push_back({(uintptr_t)l->flags, n, 1});
-        if (l->summary) r.push_back({(uintptr_t)l->summary, 5 * 4, 4});
-        r.push_back({(uintptr_t)l->rem_offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)l->rem_counts, n * 4, 4});
-        r.push_back({(uintptr_t)l->ups_offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)l->ups_counts, n * 4, 4});
-        r.push_back({(uintptr_t)l->rem_keys, 0, 8});
-        r.push_back({(uintptr_t)l->rem_actors, 0, 4});
-        r.push_back({(uintptr_t)l->rem_counters, 0, 8});
-        r.push_back({(uintptr_t)l->ups_keys, 0, 8});
-        r.push_back({(uintptr_t)l->ups_actors, 0, 4});
-        r.push_back({(uintptr_t)l->ups_counters, 0, 8});
-        if (l->ups_kind) r.push_back({(uintptr_t)l->ups_kind, 0, 1});
-    }
-    for (size_t i = 0; i < r.size(); ++i)
-        for (size_t j = i + 1; j < r.size(); ++j) {
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
-                return CRDT_E_INVALID;
-        }
-    for (const crdt_awset_batch* in : {a, b})
-        for (const Range& w : r) {
-            if (w.width == 4 && (w.p == (uintptr_t)in->offsets || w.p == (uintptr_t)in->counts || w.p == (uintptr_t)in->actors))
-                return CRDT_E_INVALID;
-            if (w.width == 8 && (w.p == (uintptr_t)in->keys || w.p == (uintptr_t)in->counters || w.p == (uintptr_t)in->vv))
-                return CRDT_E_INVALID;
-        }
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
-    if (rc != CRDT_OK) return rc;
-    if (a->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
-    auto lview = [](const crdt_merge_log* l) {
-        return MergeLogView{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
-                            l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
-                            l->ups_actors, l->ups_counters, l->ups_kind};
-    };
+                           const crdt_merge_log* log_ba, bool exchange, void* stream) {
+    if (!ctx || check_join_log(a, b, out_ab, out_ba, log_ab, log_ba, exchange) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, a->n_docs);
+    if (c.rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) c.rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (c.rc != CRDT_OK) return c.rc;
+    if (a->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
     OutView o2v;
     MergeLogView l2v;
     if (out_ba) {
         o2v = view(out_ba);
-        l2v = lview(log_ba);
+        l2v = view(log_ba);
     }
-    rc = hip_err(launch_join_log(view(a), view(b), view(out_ab), out_ba ? &o2v : nullptr, lview(log_ab),
-                                 out_ba ? &l2v : nullptr, make_work(ctx), ctx->parts.as<uint32_t>(), block_grid(ctx), s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_join_log(view(a), view(b), view(out_ab), out_ba ? &o2v : nullptr, view(log_ab),
+                                 out_ba ? &l2v : nullptr, make_work(ctx), ctx->parts.as<uint32_t>(), block_grid(ctx),
+                                 c.s));
 }
 
 int crdt_awset_join_log_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_awset_batch* src,
                               const crdt_awset_out* out, const crdt_merge_log* log, void* stream) {
-    return join_log_common(ctx, dst, src, out, nullptr, log, nullptr, stream);
+    return join_log_common(ctx, dst, src, out, nullptr, log, nullptr, false, stream);
 }
 
 int crdt_awset_exchange_log_async(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_awset_batch* b,
                                   const crdt_awset_out* out_ab, const crdt_awset_out* out_ba,
                                   const crdt_merge_log* log_ab, const crdt_merge_log* log_ba, void* stream) {
-    if (!out_ba || !log_ba) return CRDT_E_INVALID;
-    return join_log_common(ctx, a, b, out_ab, out_ba, log_ab, log_ba, stream);
+    return join_log_common(ctx, a, b, out_ab, out_ba, log_ab, log_ba, true, stream);
 }
 
 // Logged delta merge of a resident pair (delta_pair_log.hip).  Workspace: the
 // join's worklist and the summary's partial sums, as the logged join.  The
 // argument errors are the delta exchange's and the logged join's together.
 // a_tombs / a_doc_actor / a_actor: replica a beyond its state (the exchange);
-// out_ba / log_ba == NULL: the join, which reads none of them.
+// out_ba / log_ba == NULL: the join, which reads none of them.  The callers have
+// checked the arguments.
 static int delta_pair_log_common(crdt_ctx* ctx, const crdt_awset_batch* a, const crdt_tomb_batch* a_tombs,
                                  const uint32_t* a_doc_actor, uint32_t a_actor, const crdt_replica* b,
                                  const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
                                  uint8_t* kind_ba, const crdt_merge_log* log_ab, const crdt_merge_log* log_ba,
                                  void* stream) {
-    if (!ctx || !batch_ptrs_ok(a) || !b || !batch_ptrs_ok(b->state) || !out_ptrs_ok(out_ab) ||
-        (out_ba && !out_ptrs_ok(out_ba)))
-        return CRDT_E_INVALID;
-    const crdt_awset_batch* bs = b->state;
-    if (a->n_docs != bs->n_docs || a->R != bs->R) return CRDT_E_INVALID;
-    if ((a_tombs && !a_tombs->offsets) || (b->tombs && !b->tombs->offsets)) return CRDT_E_INVALID;
-    const crdt_merge_log* const logs[2] = {log_ab, log_ba};
-    const int n_logs = out_ba ? 2 : 1;
-    for (int i = 0; i < n_logs; ++i) {
-        const crdt_merge_log* l = logs[i];
-        if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
-            !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
-            return CRDT_E_INVALID;
-    }
-    // No two written arrays start at one address, the per-document arrays, whose
-    // sizes the host knows, do not overlap at all, and no written array starts
-    // where an input array of the same kind starts.
-    const size_t n = a->n_docs, R = a->R;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;  // 0: size unknown here (entry arrays)
-        int width;     // bytes per element: the array's kind
-    };
-    std::vector<Range> r;
-    for (const crdt_awset_out* o : {out_ab, out_ba}) {
-        if (!o) continue;
-        r.push_back({(uintptr_t)o->offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)o->counts, n * 4, 4});
-        r.push_back({(uintptr_t)o->vv, n * R * 8, 8});
-        r.push_back({(uintptr_t)o->keys, 0, 8});
-        r.push_back({(uintptr_t)o->actors, 0, 4});
-        r.push_back({(uintptr_t)o->counters, 0, 8});
-    }
-    for (int i = 0; i < n_logs; ++i) {
-        const crdt_merge_log* l = logs[i];
-        r.push_back({(uintptr_t)l->flags, n, 1});
-        if (l->summary) r.push_back({(uintptr_t)l->summary, 5 * 4, 4});
-        r.push_back({(uintptr_t)l->rem_offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)l->rem_counts, n * 4, 4});
-        r.push_back({(uintptr_t)l->ups_offsets, (n + 1) * 4, 4});
-        r.push_back({(uintptr_t)l->ups_counts, n * 4, 4});
-        r.push_back({(uintptr_t)l->rem_keys, 0, 8});
-        r.push_back({(uintptr_t)l->rem_actors, 0, 4});
-        r.push_back({(uintptr_t)l->rem_counters, 0, 8});
-        r.push_back({(uintptr_t)l->ups_keys, 0, 8});
-        r.push_back({(uintptr_t)l->ups_actors, 0, 4});
-        r.push_back({(uintptr_t)l->ups_counters, 0, 8});
-        if (l->ups_kind) r.push_back({(uintptr_t)l->ups_kind, 0, 1});
-    }
-    if (kind_ab) r.push_back({(uintptr_t)kind_ab, n, 1});
-    if (out_ba && kind_ba) r.push_back({(uintptr_t)kind_ba, n, 1});
-    for (size_t i = 0; i < r.size(); ++i)
-        for (size_t j = i + 1; j < r.size(); ++j) {
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
-                return CRDT_E_INVALID;
-        }
-    const crdt_tomb_batch* tb[2] = {a_tombs, b->tombs};
-    const crdt_awset_batch* st[2] = {a, bs};
-    const uint32_t* da[2] = {a_doc_actor, b->doc_actor};
-    for (int p = 0; p < 2; ++p)
-        for (const Range& w : r) {
-            if (w.width == 4) {
-                if (w.p == (uintptr_t)st[p]->offsets || w.p == (uintptr_t)st[p]->counts ||
-                    w.p == (uintptr_t)st[p]->actors || (da[p] && w.p == (uintptr_t)da[p]))
-                    return CRDT_E_INVALID;
-                if (tb[p] && (w.p == (uintptr_t)tb[p]->offsets || (tb[p]->counts && w.p == (uintptr_t)tb[p]->counts) ||
-                              (tb[p]->actors && w.p == (uintptr_t)tb[p]->actors)))
-                    return CRDT_E_INVALID;
-            }
-            if (w.width == 8) {
-                if (w.p == (uintptr_t)st[p]->keys || w.p == (uintptr_t)st[p]->counters || w.p == (uintptr_t)st[p]->vv)
-                    return CRDT_E_INVALID;
-                if (tb[p] && ((tb[p]->keys && w.p == (uintptr_t)tb[p]->keys) ||
-                              (tb[p]->counters && w.p == (uintptr_t)tb[p]->counters)))
-                    return CRDT_E_INVALID;
-            }
-        }
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(a->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
-    if (rc != CRDT_OK) return rc;
-    if (a->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
-    auto side = [](const crdt_awset_batch* st_, const crdt_tomb_batch* t, const uint32_t* doc_actor, uint32_t actor) {
-        PairSide ps{};
-        ps.st = view(st_);
-        if (t) ps.tb = TombView{t->offsets, t->counts, t->keys, t->actors, t->counters};
-        ps.doc_actor = doc_actor;
-        ps.actor = actor;
-        return ps;
-    };
-    auto lview = [](const crdt_merge_log* l) {
-        return MergeLogView{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
-                            l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
-                            l->ups_actors, l->ups_counters, l->ups_kind};
-    };
+    if (!ctx) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, a->n_docs);
+    if (c.rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) c.rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (c.rc != CRDT_OK) return c.rc;
+    if (a->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
     OutView o2v;
     MergeLogView l2v;
     if (out_ba) {
         o2v = view(out_ba);
-        l2v = lview(log_ba);
+        l2v = view(log_ba);
     }
-    rc = hip_err(launch_delta_pair_log(side(a, a_tombs, a_doc_actor, a_actor),
-                                       side(bs, b->tombs, b->doc_actor, b->actor), view(out_ab),
-                                       out_ba ? &o2v : nullptr, kind_ab, kind_ba, lview(log_ab),
+    return c.end(launch_delta_pair_log(pair_side(a, a_tombs, a_doc_actor, a_actor),
+                                       pair_side(b->state, b->tombs, b->doc_actor, b->actor), view(out_ab),
+                                       out_ba ? &o2v : nullptr, kind_ab, kind_ba, view(log_ab),
                                        out_ba ? &l2v : nullptr, make_work(ctx), ctx->parts.as<uint32_t>(),
-                                       block_grid(ctx), s));
-    return leave(ctx, s, cap, rc);
+                                       block_grid(ctx), c.s));
 }
 
 int crdt_awset_delta_join_log_async(crdt_ctx* ctx, const crdt_awset_batch* dst, const crdt_replica* src,
                                     const crdt_awset_out* out, uint8_t* kind, const crdt_merge_log* log,
                                     void* stream) {
+    if (check_delta_pair_log(dst, nullptr, nullptr, src, out, nullptr, kind, nullptr, log, nullptr) != CRDT_OK)
+        return CRDT_E_INVALID;
     return delta_pair_log_common(ctx, dst, nullptr, nullptr, 0u, src, out, nullptr, kind, nullptr, log, nullptr,
                                  stream);
 }
@@ -1493,7 +1100,8 @@ int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, co
                                         const crdt_awset_out* out_ab, const crdt_awset_out* out_ba, uint8_t* kind_ab,
                                         uint8_t* kind_ba, const crdt_merge_log* log_ab, const crdt_merge_log* log_ba,
                                         void* stream) {
-    if (!a || !out_ba || !log_ba) return CRDT_E_INVALID;
+    if (check_delta_exchange_log(a, b, out_ab, out_ba, kind_ab, kind_ba, log_ab, log_ba) != CRDT_OK)
+        return CRDT_E_INVALID;
     return delta_pair_log_common(ctx, a->state, a->tombs, a->doc_actor, a->actor, b, out_ab, out_ba, kind_ab,
                                  kind_ba, log_ab, log_ba, stream);
 }
@@ -1503,99 +1111,27 @@ int crdt_awset_delta_exchange_log_async(crdt_ctx* ctx, const crdt_replica* a, co
 // errors are the fold's and the logged join's together.
 int crdt_awset_fold_log_async(crdt_ctx* ctx, int mode, const crdt_awset_batch* dst, const crdt_src_batch* srcs,
                               const crdt_awset_out* out, const crdt_merge_log* log, void* stream) {
-    if (!ctx || !batch_ptrs_ok(dst) || !src_ptrs_ok(srcs) || !out_ptrs_ok(out)) return CRDT_E_INVALID;
-    if (mode != CRDT_FOLD_AWSET && mode != CRDT_FOLD_DELTA) return CRDT_E_INVALID;
-    if (dst->n_docs != srcs->n_docs || dst->R != srcs->R) return CRDT_E_INVALID;
-    const crdt_merge_log* l = log;
-    if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
-        !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
-        return CRDT_E_INVALID;
-    // No two written arrays start at one address, the per-document arrays, whose
-    // sizes the host knows, do not overlap at all, and no written array starts
-    // where an input array of the same kind starts.
-    const size_t n = dst->n_docs, R = dst->R;
-    struct Range {
-        uintptr_t p;
-        size_t bytes;  // 0: size unknown here (entry arrays)
-        int width;     // bytes per element: the array's kind
-    };
-    std::vector<Range> r = {{(uintptr_t)out->offsets, (n + 1) * 4, 4}, {(uintptr_t)out->counts, n * 4, 4},
-                            {(uintptr_t)out->vv, n * R * 8, 8},       {(uintptr_t)out->keys, 0, 8},
-                            {(uintptr_t)out->actors, 0, 4},           {(uintptr_t)out->counters, 0, 8},
-                            {(uintptr_t)l->flags, n, 1},              {(uintptr_t)l->rem_offsets, (n + 1) * 4, 4},
-                            {(uintptr_t)l->rem_counts, n * 4, 4},     {(uintptr_t)l->ups_offsets, (n + 1) * 4, 4},
-                            {(uintptr_t)l->ups_counts, n * 4, 4},     {(uintptr_t)l->rem_keys, 0, 8},
-                            {(uintptr_t)l->rem_actors, 0, 4},         {(uintptr_t)l->rem_counters, 0, 8},
-                            {(uintptr_t)l->ups_keys, 0, 8},           {(uintptr_t)l->ups_actors, 0, 4},
-                            {(uintptr_t)l->ups_counters, 0, 8}};
-    if (l->summary) r.push_back({(uintptr_t)l->summary, 5 * 4, 4});
-    if (l->ups_kind) r.push_back({(uintptr_t)l->ups_kind, 0, 1});
-    for (size_t i = 0; i < r.size(); ++i)
-        for (size_t j = i + 1; j < r.size(); ++j) {
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-            if (r[i].bytes && r[j].bytes && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
-                return CRDT_E_INVALID;
-        }
-    const void* const in4[] = {dst->offsets, dst->counts, dst->actors, srcs->doc_srcs, srcs->src_actor,
-                               srcs->entry_off, srcs->actors, srcs->tomb_off, srcs->tactors};
-    const void* const in8[] = {dst->keys, dst->counters, dst->vv, srcs->vv, srcs->keys, srcs->counters, srcs->tkeys,
-                               srcs->tcounters};
-    for (const Range& w : r) {
-        if (w.width == 4)
-            for (const void* q : in4)
-                if (q && w.p == (uintptr_t)q) return CRDT_E_INVALID;
-        if (w.width == 8)
-            for (const void* q : in8)
-                if (q && w.p == (uintptr_t)q) return CRDT_E_INVALID;
-    }
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->worklist, std::max<size_t>(dst->n_docs, 1) * sizeof(uint32_t), cap);
-    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
-    if (rc != CRDT_OK) return rc;
-    if (ctx->scratch_slots == 0) {
-        if (cap) return CRDT_E_WORKSPACE;
-        if (reserve_scratch(ctx, 1) != CRDT_OK) return CRDT_E_NOMEM;
-    }
-    if (dst->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), s) != hipSuccess) return CRDT_E_HIP;
-    const size_t slots = ctx->scratch_slots;
-    Scratch scr{ctx->scratch.as<uint64_t>(0), ctx->scratch.as<uint32_t>(slots * 16), ctx->scratch.as<uint64_t>(slots * 8),
-                slots};
-    const MergeLogView lv{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
-                          l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
-                          l->ups_actors, l->ups_counters, l->ups_kind};
-    rc = hip_err(launch_fold_log(mode, view(dst), view(srcs), view(out), scr, lv, make_work(ctx),
-                                 ctx->parts.as<uint32_t>(), block_grid(ctx), s));
-    return leave(ctx, s, cap, rc);
+    if (!ctx || check_fold_log(mode, dst, srcs, out, log) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->worklist, dst->n_docs);
+    if (c.rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) c.rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (c.rc != CRDT_OK) return c.rc;
+    Scratch scr;
+    if (int rc = fold_scratch(ctx, c.cap, &scr)) return rc;
+    if (dst->n_docs != 0 && launch_reset_work(ctx->ws.as<uint32_t>(0), c.s) != hipSuccess) return CRDT_E_HIP;
+    return c.end(launch_fold_log(mode, view(dst), view(srcs), view(out), scr, view(log), make_work(ctx),
+                                 ctx->parts.as<uint32_t>(), block_grid(ctx), c.s));
 }
 
 int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
                            const crdt_op_batch* ops, const crdt_awset_out* out, const crdt_tomb_out* tomb_out,
                            void* stream) {
-    if (!ctx || !batch_ptrs_ok(state) || !ops || !ops->op_off || !ops->doc_actor || !out_ptrs_ok(out))
-        return CRDT_E_INVALID;
-    if (ops->n_docs != state->n_docs) return CRDT_E_INVALID;
-    if (tombs && (!tombs->offsets || !tombs->keys || !tombs->actors || !tombs->counters)) return CRDT_E_INVALID;
-    if (tomb_out && (!tomb_out->offsets || !tomb_out->counts || !tomb_out->keys || !tomb_out->actors ||
-                     !tomb_out->counters))
-        return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
-    TombView tv{};
-    if (tombs) tv = TombView{tombs->offsets, tombs->counts, tombs->keys, tombs->actors, tombs->counters};
-    TombOut to{};
-    if (tomb_out) to = TombOut{tomb_out->offsets, tomb_out->counts, tomb_out->keys, tomb_out->actors, tomb_out->counters};
+    if (!ctx || check_apply(state, tombs, ops, out, tomb_out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
     const ApplyOps av{ops->n_docs, ops->op_off, ops->kind, ops->keys, ops->doc_actor};
-    rc = hip_err(launch_apply(view(state), tv, av, view(out), to, tomb_out != nullptr, make_work(ctx),
-                              (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_apply(view(state), view(tombs), av, view(out), view(tomb_out), tomb_out != nullptr,
+                              make_work(ctx), (uint32_t)ctx->n_cu, c.s));
 }
 
 // Logged local ops (apply_log.hip).  Workspace: the logged join's summary partial
@@ -1603,86 +1139,29 @@ int crdt_awset_apply_async(crdt_ctx* ctx, const crdt_awset_batch* state, const c
 int crdt_awset_apply_log_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
                                const crdt_op_batch* ops, const crdt_awset_out* out, const crdt_tomb_out* tomb_out,
                                const crdt_merge_log* log, void* stream) {
-    if (!ctx || !batch_ptrs_ok(state) || !ops || !ops->op_off || !ops->doc_actor || !out_ptrs_ok(out))
-        return CRDT_E_INVALID;
-    if (ops->n_docs != state->n_docs) return CRDT_E_INVALID;
-    if (tombs && (!tombs->offsets || !tombs->keys || !tombs->actors || !tombs->counters)) return CRDT_E_INVALID;
-    if (tomb_out && (!tomb_out->offsets || !tomb_out->counts || !tomb_out->keys || !tomb_out->actors ||
-                     !tomb_out->counters))
-        return CRDT_E_INVALID;
-    const crdt_merge_log* l = log;
-    if (!l || !l->flags || !l->rem_offsets || !l->rem_counts || !l->rem_keys || !l->rem_actors || !l->rem_counters ||
-        !l->ups_offsets || !l->ups_counts || !l->ups_keys || !l->ups_actors || !l->ups_counters)
-        return CRDT_E_INVALID;
-    // No two written arrays start at one address, and no written array starts where
-    // an input array of the same kind starts.
-    struct Written {
-        const void* p;
-        int width;  // bytes per element: the array's kind
-    };
-    std::vector<Written> r = {{out->offsets, 4},    {out->counts, 4},      {out->vv, 8},          {out->keys, 8},
-                              {out->actors, 4},     {out->counters, 8},    {l->flags, 1},         {l->rem_offsets, 4},
-                              {l->rem_counts, 4},   {l->ups_offsets, 4},   {l->ups_counts, 4},    {l->rem_keys, 8},
-                              {l->rem_actors, 4},   {l->rem_counters, 8},  {l->ups_keys, 8},      {l->ups_actors, 4},
-                              {l->ups_counters, 8}};
-    if (tomb_out)
-        r.insert(r.end(), {{tomb_out->offsets, 4}, {tomb_out->counts, 4}, {tomb_out->keys, 8}, {tomb_out->actors, 4},
-                           {tomb_out->counters, 8}});
-    if (l->summary) r.push_back({l->summary, 4});
-    if (l->ups_kind) r.push_back({l->ups_kind, 1});
-    for (size_t i = 0; i < r.size(); ++i)
-        for (size_t j = i + 1; j < r.size(); ++j)
-            if (r[i].p == r[j].p) return CRDT_E_INVALID;
-    std::vector<const void*> in1 = {ops->kind}, in4 = {state->offsets, state->counts, state->actors, ops->op_off,
-                                                       ops->doc_actor},
-                             in8 = {state->keys, state->counters, state->vv, ops->keys};
-    if (tombs) {
-        in4.insert(in4.end(), {tombs->offsets, tombs->counts, tombs->actors});
-        in8.insert(in8.end(), {tombs->keys, tombs->counters});
-    }
-    for (const Written& w : r)
-        for (const void* q : w.width == 1 ? in1 : w.width == 4 ? in4 : in8)
-            if (q && w.p == q) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) rc = CRDT_E_WORKSPACE;  // (sized at create: never)
-    if (rc != CRDT_OK) return rc;
-    TombView tv{};
-    if (tombs) tv = TombView{tombs->offsets, tombs->counts, tombs->keys, tombs->actors, tombs->counters};
-    TombOut to{};
-    if (tomb_out) to = TombOut{tomb_out->offsets, tomb_out->counts, tomb_out->keys, tomb_out->actors, tomb_out->counters};
+    if (!ctx || check_apply_log(state, tombs, ops, out, tomb_out, log) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    if (c.rc == CRDT_OK && ctx->parts.bytes < join_log_parts_bytes()) c.rc = CRDT_E_WORKSPACE;  // (sized at create: never)
+    if (c.rc != CRDT_OK) return c.rc;
     const ApplyOps av{ops->n_docs, ops->op_off, ops->kind, ops->keys, ops->doc_actor};
-    const MergeLogView lv{l->flags,      l->summary,   l->rem_offsets, l->rem_counts, l->rem_keys,
-                          l->rem_actors, l->rem_counters, l->ups_offsets, l->ups_counts, l->ups_keys,
-                          l->ups_actors, l->ups_counters, l->ups_kind};
-    rc = hip_err(launch_apply_log(view(state), tv, av, view(out), to, tomb_out != nullptr, lv, make_work(ctx),
-                                  ctx->parts.as<uint32_t>(), (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+    return c.end(launch_apply_log(view(state), view(tombs), av, view(out), view(tomb_out), tomb_out != nullptr,
+                                  view(log), make_work(ctx), ctx->parts.as<uint32_t>(), (uint32_t)ctx->n_cu, c.s));
 }
 
 int crdt_awset_sort_async(crdt_ctx* ctx, const crdt_awset_batch* in, uint32_t n_slots, const crdt_awset_out* out,
                           void* stream) {
-    if (!ctx || !batch_ptrs_ok(in) || !out_ptrs_ok(out) || out->keys == in->keys) return CRDT_E_INVALID;
-    if (n_slots && (!in->keys || !in->actors || !in->counters)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
+    if (!ctx || check_sort(in, n_slots, out) != CRDT_OK) return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
     size_t tb = 0;
     if (sort_storage(in->n_docs, n_slots, &tb) != hipSuccess) return CRDT_E_HIP;
-    rc = grow(ctx->sort_tmp, std::max<size_t>(tb, 16), cap);
-    if (rc == CRDT_OK) rc = grow(ctx->sort_idx, std::max<size_t>(n_slots, 1) * 4, cap);
-    if (rc == CRDT_OK) rc = grow(ctx->sort_ends, std::max<size_t>(in->n_docs, 1) * 4, cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_sort(view(in), n_slots, view(out), ctx->sort_tmp.p, ctx->sort_tmp.bytes,
+    c.need_bytes(ctx->sort_tmp, std::max<size_t>(tb, 16));
+    c.need(ctx->sort_idx, n_slots);
+    c.need(ctx->sort_ends, in->n_docs);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_sort(view(in), n_slots, view(out), ctx->sort_tmp.p, ctx->sort_tmp.bytes,
                              ctx->sort_ends.as<uint32_t>(), ctx->sort_idx.as<uint32_t>(), ctx->ws.as<uint32_t>(64),
-                             (uint32_t)ctx->n_cu, s));
-    return leave(ctx, s, cap, rc);
+                             (uint32_t)ctx->n_cu, c.s));
 }
 
 int crdt_vv_min_async(crdt_ctx* ctx, uint64_t* dst, const uint64_t* src, size_t n, void* stream) {
@@ -1699,9 +1178,8 @@ int crdt_tombstone_gc_async(crdt_ctx* ctx, const crdt_tomb_batch* tombs, uint32_
         return CRDT_E_INVALID;
     int rc = set_device(ctx);
     if (rc != CRDT_OK) return rc;
-    const TombView tv{tombs->offsets, tombs->counts, tombs->keys, tombs->actors, tombs->counters};
-    const TombOut to{out->offsets, out->counts, out->keys, out->actors, out->counters};
-    return hip_err(launch_tomb_gc(tv, n_docs, R, stable_vv, to, (uint32_t)ctx->n_cu, (hipStream_t)stream));
+    return hip_err(launch_tomb_gc(view(tombs), n_docs, R, stable_vv, view(out), (uint32_t)ctx->n_cu,
+                                  (hipStream_t)stream));
 }
 
 int crdt_vv_max_async(crdt_ctx* ctx, uint64_t* dst, const uint64_t* src, size_t n, void* stream) {
@@ -1714,15 +1192,10 @@ int crdt_vv_max_async(crdt_ctx* ctx, uint64_t* dst, const uint64_t* src, size_t 
 int crdt_causal_context_async(crdt_ctx* ctx, const uint64_t* vv, uint32_t n_docs, uint32_t R, uint64_t* out,
                               void* stream) {
     if (!ctx || !out || R == 0 || R > CRDT_MAX_R || (n_docs && !vv)) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    uint32_t n_part = std::min<uint32_t>(kCtxParts, std::max<uint32_t>(1u, (n_docs + 255) / 256));
-    hipStream_t s = (hipStream_t)stream;
-    bool cap = false;
-    rc = enter(ctx, s, cap);
-    if (rc != CRDT_OK) return rc;
-    rc = hip_err(launch_context(vv, n_docs, R, ctx->parts.as<uint64_t>(), n_part, out, s));
-    return leave(ctx, s, cap, rc);
+    const uint32_t n_part = std::min<uint32_t>(kCtxParts, std::max<uint32_t>(1u, (n_docs + 255) / 256));
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_context(vv, n_docs, R, ctx->parts.as<uint64_t>(), n_part, out, c.s));
 }
 
 int crdt_gen_pair_async(crdt_ctx* ctx, uint64_t seed, uint32_t n_docs, const crdt_awset_out* a,
@@ -1785,15 +1258,13 @@ int crdt_bw_probe(crdt_ctx* ctx, int kind, const void* a, void* b, size_t bytes,
     if (!ctx || !gbs || kind < CRDT_PROBE_READ || kind > CRDT_PROBE_MIX_PLAIN || reps < 1 || bytes < 16 || !b ||
         (kind != CRDT_PROBE_WRITE && kind != CRDT_PROBE_WRITE_PLAIN && !a))
         return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = ctx->stream;
-    bool cap = false;
-    if ((rc = enter(ctx, s, cap)) != CRDT_OK) return rc;
-    if (cap) return CRDT_E_INVALID;
+    Call c(ctx, ctx->stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    if (c.cap) return CRDT_E_INVALID;
+    const hipStream_t s = c.s;
     const size_t n16 = bytes / 16;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    rc = hip_err(hipEventCreate(&e0));
+    int rc = hip_err(hipEventCreate(&e0));
     if (rc == CRDT_OK) rc = hip_err(hipEventCreate(&e1));
     // one untimed launch (first touch, clocks up), then reps timed back to back
     if (rc == CRDT_OK) rc = hip_err(launch_probe(kind, a, b, n16, (uint32_t)ctx->n_cu, ctx->probe_blocks_per_cu, ctx->probe_slab, s));
@@ -1812,7 +1283,7 @@ int crdt_bw_probe(crdt_ctx* ctx, int kind, const void* a, void* b, size_t bytes,
                                  : (double)n16 * 16.0 * ((kind == CRDT_PROBE_COPY || kind == CRDT_PROBE_COPY_PLAIN) ? 2.0 : 1.0);
         *gbs = ms > 0.f ? moved * reps / (ms * 1e-3) / 1e9 : 0.0;
     }
-    return leave(ctx, s, cap, rc);
+    return c.end(rc);
 }
 
 int crdt_host_alloc(size_t bytes, void** out) {
@@ -1844,23 +1315,21 @@ void crdt_host_free(void* p) {
 
 int crdt_clock_probe(crdt_ctx* ctx, double* mhz) {
     if (!ctx || !mhz) return CRDT_E_INVALID;
-    int rc = set_device(ctx);
-    if (rc != CRDT_OK) return rc;
-    hipStream_t s = ctx->stream;
-    bool cap = false;
-    if ((rc = enter(ctx, s, cap)) != CRDT_OK) return rc;
-    if (cap) return CRDT_E_INVALID;
+    Call c(ctx, ctx->stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    if (c.cap) return CRDT_E_INVALID;
+    const hipStream_t s = c.s;
     int wall_khz = 0;
     if (hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || wall_khz <= 0)
         return CRDT_E_HIP;
     uint64_t* dev = ctx->parts.as<uint64_t>();  // 3 words of the context-summary partials, free between calls
     uint64_t host[2] = {0, 0};
-    rc = hip_err(launch_clock_probe(dev, (uint32_t)ctx->n_cu, s));  // warm-up: clocks ramp up
+    int rc = hip_err(launch_clock_probe(dev, (uint32_t)ctx->n_cu, s));  // warm-up: clocks ramp up
     if (rc == CRDT_OK) rc = hip_err(launch_clock_probe(dev, (uint32_t)ctx->n_cu, s));
     if (rc == CRDT_OK) rc = hip_err(hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, s));
     if (rc == CRDT_OK) rc = hip_err(hipStreamSynchronize(s));
     if (rc == CRDT_OK) *mhz = host[1] ? (double)host[0] / ((double)host[1] / ((double)wall_khz * 1e3)) / 1e6 : 0.0;
-    return leave(ctx, s, cap, rc);
+    return c.end(rc);
 }
 
 /* ---------------- validation (host) ---------------- */
