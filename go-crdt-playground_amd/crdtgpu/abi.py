@@ -44,6 +44,8 @@ CRDT_DIFF_UPDATED = 4
 CRDT_DIFF_CLOCK = 8
 CRDT_DIG_ELEMENTS = 1
 CRDT_DIG_STATE = 2
+CRDT_DIGEST_GATHER = 0
+CRDT_DIGEST_PLACE = 1
 CRDT_OP_ADD = 0
 CRDT_OP_DEL = 1
 CRDT_OP_DELTA_DEL = 2
@@ -239,6 +241,8 @@ def signatures():
         "crdt_awset_digest_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp]),
         "crdt_awset_digest_host": (ctypes.c_int, [P(CAWSetBatch), P(CTombBatch), _vp]),
         "crdt_digest_diff_async": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, P(CCompareOut), _vp]),
+        "crdt_awset_digest_idx_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp, _u32, _u32, _u32,
+                                                        _vp, _vp]),
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_sources_async": (ctypes.c_int, [_vp, P(CReplica), _u32, _u32, _u32, P(CDeltaOut), _vp]),

@@ -318,6 +318,45 @@ class Engine:
         self.sync()
         return _np(out, np.uint64)[: 2 * state.n_docs].reshape(state.n_docs, 2)
 
+    def digest_idx_async(self, state: AWSetBatch, idx, digest, tombs: TombBatch = None, n_idx=None, n_max=None,
+                         mode: int = abi.CRDT_DIGEST_GATHER, stream=None):
+        """The digests of the listed docs only, written into `digest` (device u64, two words
+        per doc of the replica) at their own positions; every other word keeps its bits
+        (crdt_awset_digest_idx_async).  GATHER: state is the replica, doc idx[j] is digested.
+        PLACE: state is a sub-batch whose doc j is the replica's doc idx[j].  idx / n_idx:
+        device u32 arrays (a worklist / n_work); n_idx None: n_max; n_max None: len(idx)."""
+        s = _c(state)
+        t = _c(tombs) if tombs is not None else None
+        n_max = int(idx.shape[0]) if n_max is None else int(n_max)
+        n_digest = int(digest.shape[0]) // 2  # (GATHER: the call refuses an array that is not the replica's length)
+        check(self._lib.crdt_awset_digest_idx_async(self._ctx, ctypes.byref(s), ctypes.byref(t) if t else None,
+                                                    ptr(idx), ptr(n_idx), n_max, n_digest, int(mode), ptr(digest),
+                                                    _stream(stream)), "crdt_awset_digest_idx_async")
+
+    def digest_idx(self, state: AWSetBatch, idx, digest, tombs: TombBatch = None, mode: int = abi.CRDT_DIGEST_GATHER):
+        """Host batch, host list and host digest array (numpy u64 [n_docs, 2]) uploaded, the
+        listed docs re-digested on the device: the updated array, numpy u64 [n_docs, 2] (for
+        tests and small callers)."""
+        import numpy as np
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        state = state.numpy()
+        digest = np.ascontiguousarray(digest, np.uint64).reshape(-1, 2)
+        idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        out = torch.zeros(max(2 * len(digest), 2), dtype=torch.int64, device=dev)
+        out[: 2 * len(digest)] = torch.from_numpy(digest.reshape(-1).view(np.int64).copy()).to(dev)
+        di = torch.zeros(max(len(idx), 1), dtype=torch.int32, device=dev)
+        di[: len(idx)] = torch.from_numpy(idx.view(np.int32).copy()).to(dev)
+        ds, dt = state.to(dev), tombs.numpy().to(dev) if tombs is not None else None
+        s = ds.c()
+        t = dt.c() if dt is not None else None
+        check(self._lib.crdt_awset_digest_idx_async(self._ctx, ctypes.byref(s), ctypes.byref(t) if t else None,
+                                                    ptr(di), None, len(idx), len(digest), int(mode), ptr(out), None),
+              "crdt_awset_digest_idx_async")
+        self.sync()
+        return _np(out, np.uint64)[: 2 * len(digest)].reshape(len(digest), 2)
+
     def digest_diff_async(self, mine, theirs, n_docs: int, out: CompareBuffers, mask: int = 3, stream=None):
         """Per doc, CRDT_DIG_ELEMENTS / CRDT_DIG_STATE of two digest arrays (device u64
         [2 * n_docs]), the summary counts and the ascending worklist of docs with flags & mask,

@@ -82,6 +82,9 @@ hipError_t launch_apply_log(const BatchView& st, const TombView& tb, const Apply
                             uint32_t* parts, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, uint64_t* digest,
                          uint32_t* status, uint32_t n_cu, hipStream_t stream);
+hipError_t launch_digest_idx(const HasView& st, const HasView& tb, const uint64_t* vv, uint32_t R, const uint32_t* idx,
+                             const uint32_t* n_idx, uint32_t n_max, uint32_t n_digest, uint32_t mode, uint64_t* digest,
+                             uint32_t* status, uint32_t n_cu, hipStream_t stream);
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
                               const CompareOutView& out, uint32_t* fw, const uint32_t* gate, uint32_t n_cu,
                               hipStream_t stream);
@@ -775,6 +778,20 @@ int crdt_awset_digest_async(crdt_ctx* ctx, const crdt_awset_batch* state, const 
     if (c.rc != CRDT_OK) return c.rc;
     return c.end(launch_digest(has_view(state), has_view(tombs, state->n_docs), state->vv, state->R, digest,
                                make_work(ctx).status, (uint32_t)ctx->n_cu, c.s));
+}
+
+// Worklist digests (digest_idx.hip): each listed document has one owner, no workspace.
+int crdt_awset_digest_idx_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs,
+                                const uint32_t* idx, const uint32_t* n_idx, uint32_t n_max, uint32_t n_digest_docs,
+                                uint32_t mode, uint64_t* digest, void* stream) {
+    if (!ctx || check_digest_idx(state, tombs, idx, n_idx, n_max, n_digest_docs, mode, digest) != CRDT_OK)
+        return CRDT_E_INVALID;
+    if (n_max == 0) return CRDT_OK;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest_idx(has_view(state), has_view(tombs, state->n_docs), state->vv, state->R, idx, n_idx,
+                                   n_max, n_digest_docs, mode, digest, make_work(ctx).status, (uint32_t)ctx->n_cu,
+                                   c.s));
 }
 
 // Digest comparison (digest.hip, then compare.hip's worklist step): the flag

@@ -421,6 +421,28 @@ inline int check_digest(const crdt_awset_batch* state, const crdt_tomb_batch* to
     return CRDT_OK;
 }
 
+// The worklist digest: check_digest's rules, the mode and its document counts, and
+// the list against the same inputs.
+inline int check_digest_idx(const crdt_awset_batch* state, const crdt_tomb_batch* tombs, const uint32_t* idx,
+                            const uint32_t* n_idx, uint32_t n_max, uint32_t n_digest_docs, uint32_t mode,
+                            const uint64_t* digest) {
+    if (!batch_ptrs_ok(state) || !idx || !digest || (tombs && !tomb_batch_ok(tombs, false))) return CRDT_E_INVALID;
+    if (mode > CRDT_DIGEST_PLACE) return CRDT_E_INVALID;
+    if (mode == CRDT_DIGEST_GATHER ? n_digest_docs != state->n_docs : state->n_docs < n_max) return CRDT_E_INVALID;
+    Arrays w, in, list;
+    in.add_batch(state);
+    in.add_tombs(tombs);
+    list.add(idx, 4);
+    // any_width, as check_digest: the list is refused on every array of the replica, whatever its kind
+    if (!off_inputs(list, in, true)) return CRDT_E_INVALID;
+    // the one written array, against the replica, the list and its length
+    in.add(idx, 4);
+    in.add(n_idx, 4);
+    w.add(digest, 8);
+    if (!off_inputs(w, in, true)) return CRDT_E_INVALID;
+    return CRDT_OK;
+}
+
 inline int check_compare(const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
                          const crdt_compare_out* out) {
     if (!batch_ptrs_ok(a) || !batch_ptrs_ok(b) || !compare_out_ok(out, mask)) return CRDT_E_INVALID;

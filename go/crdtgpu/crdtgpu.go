@@ -1088,6 +1088,33 @@ func (b *HostBatch) Digest() ([][2]uint64, error) {
 	return out, nil
 }
 
+// Digest modes of DigestIdx.
+const (
+	DigestGather = uint32(C.CRDT_DIGEST_GATHER) // document idx[j] of state -> digest[2*idx[j]], [2*idx[j]+1]
+	DigestPlace  = uint32(C.CRDT_DIGEST_PLACE)  // document j of state (a sub-batch) -> the same words
+)
+
+// DigestIdx re-digests only the documents a device worklist names
+// (crdt_awset_digest_idx_async) and writes their two words into digest, the
+// resident array of nDigestDocs documents, at their own positions; every other
+// word keeps its bits. DigestGather: state (and tombs) is the resident replica
+// and nDigestDocs its document count. DigestPlace: state is a sub-batch of at
+// least nMax documents whose document j is the replica's document idx[j]; a
+// target named twice is the caller's error and is not checked. idx, nIdx and
+// digest are device pointers; nIdx may be nil (nMax documents), tombs may be nil.
+// Asynchronous on stream; device-side errors surface at the context's next sync.
+func (e *Engine) DigestIdx(state *C.crdt_awset_batch, tombs *C.crdt_tomb_batch, idx, nIdx *C.uint32_t,
+	nMax, nDigestDocs, mode uint32, digest *C.uint64_t, stream unsafe.Pointer) error {
+	if state == nil || idx == nil || digest == nil {
+		return fmt.Errorf("DigestIdx: nil argument")
+	}
+	if rc := C.crdt_awset_digest_idx_async(e.ctx, state, tombs, idx, nIdx, C.uint32_t(nMax), C.uint32_t(nDigestDocs),
+		C.uint32_t(mode), digest, stream); rc != 0 {
+		return errOf("crdt_awset_digest_idx_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- merge diff
 
 // DocDiff is what turns one document's `before` into its `after`: merge's

@@ -38,6 +38,9 @@
  *       the same question across GPUs or hosts: a 16-byte hash of each
  *       document's live state, and the comparison of two such arrays (no
  *       reference counterpart: its replicas meet in one process)
+ *   crdt_awset_digest_idx_async
+ *       the digests of the documents a worklist names, written into a
+ *       resident digest array at their own positions (no reference counterpart)
  *   crdt_awset_select_async
  *       those documents (or all of them: compaction) gathered into a packed
  *       batch for the next round (no reference counterpart)
@@ -602,6 +605,52 @@ int crdt_awset_digest_host(const crdt_awset_batch* state, const crdt_tomb_batch*
                            uint64_t* digest);
 int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* theirs, uint32_t n_docs, uint32_t mask,
                            const crdt_compare_out* out, void* stream);
+
+/* ---- worklist digests: re-digest only the documents a round changed ---------
+ * A caller who keeps a digest array beside a resident replica brings it up to
+ * date after a sparse round without reading the replica whole: the call hashes
+ * only the documents idx[0 .. min(*n_idx, n_max)) names and writes their two
+ * words into `digest` ([2*n_digest_docs] u64 on the device) at their own
+ * positions.  Every other word of `digest` keeps the bits it had: none is read
+ * or written.
+ *   CRDT_DIGEST_GATHER  `state` (and tombs) is the resident replica; document
+ *       idx[j] of it goes to digest[2*idx[j]], digest[2*idx[j]+1].
+ *       n_digest_docs must equal state->n_docs.  The form used after
+ *       crdt_replica_scatter_inplace_async, crdt_replica_scatter_async or a
+ *       sparse apply.
+ *   CRDT_DIGEST_PLACE   `state` is a packed or merge-output sub-batch of at least
+ *       n_max documents whose document j is the replica's document idx[j]; it
+ *       goes to digest[2*idx[j]], digest[2*idx[j]+1]: the merged selection is
+ *       digested straight into the replica's array, before or without the
+ *       scatter.  state->n_docs >= n_max is required.
+ * The two words written are bit for bit what crdt_awset_digest_async and
+ * crdt_awset_digest_host give for that document (the definition above: live
+ * prefix only, clamped counts, tombstones, the clock without its R padding,
+ * (0, 0) for an empty document with a zero clock), the same on every run.
+ * idx (device) may be in any order.  In GATHER it may repeat: every writer of a
+ * word writes the same bits.  In PLACE a repeated target is the caller's error
+ * and is NOT checked: which of the sub-batch documents' digests stays is
+ * unspecified.  n_idx (device, one word) == NULL means n_max; *n_idx is read on
+ * the device, so the worklist and n_work of crdt_awset_compare_async or
+ * crdt_digest_diff_async, and spill_doc and n_spill of the in-place scatter, feed
+ * this call with no host round trip.  Reported by crdt_ctx_sync:
+ *   CRDT_E_CAPACITY  *n_idx > n_max (clamped to n_max), or a live count above its
+ *                    slots (clamped to them, as in crdt_awset_digest_async)
+ *   CRDT_E_INVALID   idx[j] >= n_digest_docs (in GATHER also >= state->n_docs):
+ *                    nothing is written for that j, every other j is exact
+ * Returned by the call, CRDT_E_INVALID: NULL state, idx or digest, R out of
+ * range, tombs without offsets, mode above 1, n_digest_docs != state->n_docs in
+ * GATHER, state->n_docs < n_max in PLACE, digest or idx starting where an input
+ * array starts (digest also where idx or n_idx starts).
+ * No workspace, no allocation, no host sync, kernel nodes only, capturable on an
+ * unreserved context; ordered after the context's previous call like every entry
+ * point.  n_max == 0 launches nothing.  One wavefront digests a listed document
+ * of up to 2,048 live entries plus tombstones, one workgroup a larger one. */
+#define CRDT_DIGEST_GATHER 0u /* document idx[j] of `state`          -> digest[2*idx[j]], digest[2*idx[j]+1] */
+#define CRDT_DIGEST_PLACE  1u /* document j of `state` (a sub-batch) -> digest[2*idx[j]], digest[2*idx[j]+1] */
+int crdt_awset_digest_idx_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs /* or NULL */,
+                                const uint32_t* idx, const uint32_t* n_idx /* or NULL */, uint32_t n_max,
+                                uint32_t n_digest_docs, uint32_t mode, uint64_t* digest, void* stream);
 
 /* ---- select: a subset of documents (or all: compaction) as a packed batch --
  * out gets n_out documents packed with no slack: out->offsets[j] is the
