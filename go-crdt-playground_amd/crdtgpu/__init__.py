@@ -9,10 +9,10 @@ from .abi import (CRDT_E_ACTOR_RANGE, CRDT_E_CAPACITY, CRDT_E_DUP_KEY, CRDT_E_HI
                   CRDT_OP_ADD, CRDT_OP_DEL, CRDT_OP_DELTA_DEL, CRDT_OP_DELTA_DEL_KEY,
                   CRDT_DELTA_NONE, CRDT_DELTA_DELTA, CRDT_DELTA_FULL,
                   CRDT_CMP_KEYS, CRDT_CMP_DOTS, CRDT_CMP_A_AHEAD, CRDT_CMP_B_AHEAD, CRDT_DIG_ELEMENTS, CRDT_DIG_STATE,
-                  CRDT_DIGEST_GATHER, CRDT_DIGEST_PLACE,
+                  CRDT_DIGEST_GATHER, CRDT_DIGEST_PLACE, CRDT_DIGEST_TREE_FANOUT,
                   CRDT_DIFF_REMOVED, CRDT_DIFF_ADDED, CRDT_DIFF_UPDATED, CRDT_DIFF_CLOCK,
                   CrdtError, LIB_PATH, header_functions, lib, strerror)
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers,  # noqa: F401
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, DigestTreeBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers,  # noqa: F401
                     TombBatch, TombBuffers, repack_slots)
-from .engine import (Engine, comm_unique_id, digest_host, dump_batch, format_doc, global_context_allreduce,  # noqa: F401
+from .engine import (Engine, comm_unique_id, digest_host, digest_tree_host, digest_tree_layout, dump_batch, format_doc, global_context_allreduce,  # noqa: F401
                      load_batch, validate, validate_src)

@@ -46,6 +46,7 @@ CRDT_DIG_ELEMENTS = 1
 CRDT_DIG_STATE = 2
 CRDT_DIGEST_GATHER = 0
 CRDT_DIGEST_PLACE = 1
+CRDT_DIGEST_TREE_FANOUT = 16
 CRDT_OP_ADD = 0
 CRDT_OP_DEL = 1
 CRDT_OP_DELTA_DEL = 2
@@ -243,6 +244,12 @@ def signatures():
         "crdt_digest_diff_async": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, P(CCompareOut), _vp]),
         "crdt_awset_digest_idx_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CTombBatch), _vp, _vp, _u32, _u32, _u32,
                                                         _vp, _vp]),
+        "crdt_digest_tree_layout": (ctypes.c_int, [_u32, _vp, _vp]),
+        "crdt_digest_tree_host": (ctypes.c_int, [_vp, _u32, _vp]),
+        "crdt_digest_tree_async": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp]),
+        "crdt_digest_tree_children_async": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+        "crdt_digest_tree_diff_async": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp,
+                                                        _u32, _vp, _vp]),
         "crdt_awset_select_async": (ctypes.c_int, [_vp, P(CAWSetBatch), _vp, _vp, _u32, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_scatter_async": (ctypes.c_int, [_vp, P(CAWSetBatch), P(CAWSetBatch), _vp, _vp, _u32, P(CAWSetOut), _vp]),
         "crdt_awset_sources_async": (ctypes.c_int, [_vp, P(CReplica), _u32, _u32, _u32, P(CDeltaOut), _vp]),

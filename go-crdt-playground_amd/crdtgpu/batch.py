@@ -549,6 +549,47 @@ class SpillBuffers:
         return _np(self.spill_j, U32)[:n].copy(), _np(self.spill_doc, U32)[:n].copy()
 
 
+class DigestTreeBuffers:
+    """The digest tree over a digest array of n_docs docs (crdt_digest_tree_async) and the
+    buffers of a descent over it: `tree` (u64, two words per node, levels 1 .. L
+    concatenated), and for lists of up to `cap` nodes or docs per level the packed children
+    (`packed`, 32 words per listed parent), two list / count pairs used in turn (`idx`,
+    `n_out`), the last level's `flags` and `summary`.  cap None: no descent buffers.
+    numpy, or torch on `device`.  L, nodes[l] and off[l] are the layout
+    (crdt_digest_tree_layout)."""
+
+    def __init__(self, n_docs, device=None, cap=None):
+        from .abi import lib
+
+        self.n_docs = int(n_docs)
+        nodes, off = np.zeros(9, U32), np.zeros(9, U32)
+        self.L = int(lib().crdt_digest_tree_layout(self.n_docs, nodes.ctypes.data, off.ctypes.data))
+        self.nodes, self.off = [int(x) for x in nodes], [int(x) for x in off]
+        self.n_nodes = self.off[self.L] + 1 if self.L else 0
+        self.cap = None if cap is None else max(int(cap), 16)  # (16: the root's children)
+        if device is None:
+            e = lambda k, dt: np.zeros(max(k, 1), dt)  # noqa: E731
+            u64, u32, u8 = np.uint64, U32, np.uint8
+        else:
+            import torch
+
+            e = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device=device)  # noqa: E731
+            u64, u32, u8 = torch.int64, torch.int32, torch.uint8
+        self.tree = e(2 * self.n_nodes, u64)
+        if self.cap is not None:
+            self.packed = e(32 * self.cap, u64)
+            self.idx = [e(self.cap, u32), e(self.cap, u32)]
+            self.n_out = [e(1, u32), e(1, u32)]
+            self.flags = e(self.cap, u8)
+            self.summary = e(5, u32)
+
+    def level(self, l, digest):
+        """(node array of level l, its node count): the digest array at l == 0."""
+        if l == 0:
+            return digest, self.n_docs
+        return self.tree[2 * self.off[l]: 2 * (self.off[l] + self.nodes[l])], self.nodes[l]
+
+
 class QueryBatch:
     """Per doc a list of query keys (crdt_query_batch): doc d asks
     keys[q_off[d]:q_off[d+1]], in any order, duplicates allowed."""

@@ -6,7 +6,7 @@ import ctypes
 
 from . import abi
 from .abi import check
-from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers, TombBatch,
+from .batch import (AWSetBatch, CompareBuffers, DiffBuffers, DigestTreeBuffers, Headroom, InplaceTarget, MergeLogBuffers, OpBatch, OutBuffers, QueryBatch, QueryBuffers, Replica, ReplicaBuffers, SpillBuffers, SrcBatch, SrcBuffers, TombBatch,
                     TombBuffers, _np, ptr)
 
 
@@ -364,6 +364,93 @@ class Engine:
         co = _c(out)
         check(self._lib.crdt_digest_diff_async(self._ctx, ptr(mine), ptr(theirs), int(n_docs), int(mask),
                                                ctypes.byref(co), _stream(stream)), "crdt_digest_diff_async")
+
+    def digest_tree_async(self, digest, n_docs: int, tree, stream=None):
+        """The hash tree of fan-out 16 over a digest array (device u64 [2 * n_docs]) into
+        `tree` (device u64, DigestTreeBuffers.tree), every level (crdt_digest_tree_async)."""
+        check(self._lib.crdt_digest_tree_async(self._ctx, ptr(digest), int(n_docs), ptr(tree), _stream(stream)),
+              "crdt_digest_tree_async")
+
+    def digest_tree(self, digest):
+        """Host digest array (numpy u64 [n_docs, 2]) uploaded and its tree built on the
+        device: numpy u64 [n_nodes, 2] (for tests and small callers: digest_tree_host)."""
+        import numpy as np
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        digest = np.ascontiguousarray(digest, np.uint64).reshape(-1, 2)
+        bufs = DigestTreeBuffers(len(digest), dev)
+        d = torch.zeros(max(2 * len(digest), 2), dtype=torch.int64, device=dev)
+        d[: 2 * len(digest)] = torch.from_numpy(digest.reshape(-1).view(np.int64).copy()).to(dev)
+        self.digest_tree_async(d, len(digest), bufs.tree)
+        self.sync()
+        return _np(bufs.tree, np.uint64)[: 2 * bufs.n_nodes].reshape(bufs.n_nodes, 2)
+
+    def digest_tree_children_async(self, level, n_level: int, out, parents=None, n_parents=None, n_max=None,
+                                   stream=None):
+        """The sender's side of a descent: both words of the 16 children of every listed
+        parent, packed into `out` (device u64, 32 words per parent), zeros past the level
+        (crdt_digest_tree_children_async).  level: the node array the children lie in
+        (DigestTreeBuffers.level).  parents / n_parents: device u32 list and count (a diff's
+        idx_out / n_out); parents None: the identity, n_parents None: n_max."""
+        n_max = int(parents.shape[0]) if n_max is None else int(n_max)
+        check(self._lib.crdt_digest_tree_children_async(self._ctx, ptr(level), int(n_level), ptr(parents),
+                                                        ptr(n_parents), n_max, ptr(out), _stream(stream)),
+              "crdt_digest_tree_children_async")
+
+    def digest_tree_diff_async(self, mine_level, n_level: int, theirs, idx_out, n_out, parents=None, n_parents=None,
+                               n_max=None, leaf: bool = False, mask: int = 3, flags_out=None, out_max=None,
+                               summary=None, stream=None):
+        """The receiver's side: the listed parents' children of its own level against the
+        peer's packed ones (`theirs`); the children with flag & mask ascending into idx_out,
+        their flags into flags_out, their exact number into n_out (crdt_digest_tree_diff_async).
+        leaf: the children are docs, flags as digest_diff_async; else nodes, bit 0 word 0
+        differs, bit 1 word 1 differs.  idx_out / n_out are the next level's parents /
+        n_parents.  out_max None: len(idx_out)."""
+        n_max = int(parents.shape[0]) if n_max is None else int(n_max)
+        out_max = int(idx_out.shape[0]) if out_max is None else int(out_max)
+        check(self._lib.crdt_digest_tree_diff_async(self._ctx, ptr(mine_level), int(n_level), ptr(theirs),
+                                                    ptr(parents), ptr(n_parents), n_max, 1 if leaf else 0, int(mask),
+                                                    ptr(idx_out), ptr(flags_out), ptr(n_out), out_max, ptr(summary),
+                                                    _stream(stream)), "crdt_digest_tree_diff_async")
+
+    def digest_tree_descend(self, digest, tree: DigestTreeBuffers, fetch, mask: int = 3, start_level=None,
+                            stream=None):
+        """Drive a descent from level `start_level` (None: the root) down to the docs.
+        fetch(level, parents, n) stands for the network: it returns the peer's packed
+        children (device u64 [32 * n]) of the n nodes of `level` that the device list
+        `parents` names (None: nodes 0 .. n - 1), as the peer's digest_tree_children_async
+        writes them.  Between levels only the 4-byte n_out is read, to size the next
+        request.  Returns (worklist, flags, n, bytes_fetched): device u32 doc ids ascending,
+        their u8 flags (CRDT_DIG_*), their number, and 256 B per parent asked for.  The
+        lists live in `tree` (built with cap >= the largest list of any level) and are
+        overwritten by the next descent.  A list above cap raises CRDT_E_CAPACITY."""
+        import numpy as np
+
+        if tree.cap is None:
+            raise ValueError("digest_tree_descend needs DigestTreeBuffers built with cap: the lists' room")
+        if tree.L == 0:
+            return tree.idx[0][:0], tree.flags[:0], 0, 0
+        lvl = tree.L if start_level is None else int(start_level)
+        if not 1 <= lvl <= tree.L:
+            raise ValueError("start_level must be 1 .. L")
+        parents, n = None, tree.nodes[lvl]
+        if n > tree.cap:
+            raise ValueError("start level holds more nodes than the buffers' cap")
+        fetched, k = 0, 0
+        while lvl >= 1:
+            theirs = fetch(lvl, parents, n)
+            fetched += 256 * n
+            mine, n_level = tree.level(lvl - 1, digest)
+            self.digest_tree_diff_async(mine, n_level, theirs, tree.idx[k], tree.n_out[k], parents=parents, n_max=n,
+                                        leaf=lvl == 1, mask=mask, flags_out=tree.flags, out_max=tree.cap,
+                                        summary=tree.summary, stream=stream)
+            self.sync(stream)  # (also where a list above cap surfaces)
+            n = int(_np(tree.n_out[k], np.uint32)[0])
+            parents, k, lvl = tree.idx[k], k ^ 1, lvl - 1
+            if n == 0:
+                break
+        return parents[:n], tree.flags[:n], n, fetched
 
     def select_async(self, state: AWSetBatch, out: OutBuffers, idx=None, n_idx=None, n_out=None, out_slots=None,
                      stream=None):
@@ -915,6 +1002,30 @@ def digest_host(batch: AWSetBatch, tombs: TombBatch = None):
     check(abi.lib().crdt_awset_digest_host(ctypes.byref(cb), ctypes.byref(ct) if ct else None, out.ctypes.data),
           "crdt_awset_digest_host")
     return out[: 2 * b.n_docs].reshape(b.n_docs, 2)
+
+
+def digest_tree_layout(n_docs: int):
+    """(L, nodes, off) of the digest tree over n_docs docs: nodes[l] the nodes of level l
+    (nodes[0] = n_docs), off[l] the node offset of level l >= 1 in the tree array
+    (crdt_digest_tree_layout)."""
+    import numpy as np
+
+    nodes, off = np.zeros(9, np.uint32), np.zeros(9, np.uint32)
+    L = abi.lib().crdt_digest_tree_layout(int(n_docs), nodes.ctypes.data, off.ctypes.data)
+    return int(L), [int(x) for x in nodes], [int(x) for x in off]
+
+
+def digest_tree_host(digest):
+    """The digest tree of a host digest array (numpy u64 [n_docs, 2]), numpy u64
+    [n_nodes, 2], levels 1 .. L concatenated (crdt_digest_tree_host: no GPU)."""
+    import numpy as np
+
+    digest = np.ascontiguousarray(digest, np.uint64).reshape(-1, 2)
+    L, nodes, off = digest_tree_layout(len(digest))
+    n_nodes = off[L] + 1 if L else 0
+    out = np.zeros(max(2 * n_nodes, 1), dtype=np.uint64)
+    check(abi.lib().crdt_digest_tree_host(digest.ctypes.data, len(digest), out.ctypes.data), "crdt_digest_tree_host")
+    return out[: 2 * n_nodes].reshape(n_nodes, 2)
 
 
 def validate(batch: AWSetBatch) -> int:

@@ -88,6 +88,16 @@ hipError_t launch_digest_idx(const HasView& st, const HasView& tb, const uint64_
 hipError_t launch_digest_diff(const uint64_t* mine, const uint64_t* theirs, uint32_t n, uint32_t mask,
                               const CompareOutView& out, uint32_t* fw, const uint32_t* gate, uint32_t n_cu,
                               hipStream_t stream);
+hipError_t launch_digest_tree(const uint64_t* digest, uint32_t n_docs, uint64_t* tree, bool fuse, hipStream_t stream);
+hipError_t launch_digest_tree_children(const uint64_t* level, uint32_t n_level, const uint32_t* parents,
+                                       const uint32_t* n_parents, uint32_t n_max, uint64_t* out, uint32_t* status,
+                                       hipStream_t stream);
+size_t digest_tree_diff_parts(uint32_t n_max);
+hipError_t launch_digest_tree_diff(const uint64_t* mine_level, uint32_t n_level, const uint64_t* theirs,
+                                   const uint32_t* parents, const uint32_t* n_parents, uint32_t n_max, uint32_t leaf,
+                                   uint32_t mask, uint32_t* idx_out, uint8_t* flags_out, uint32_t* n_out,
+                                   uint32_t out_max, uint32_t* summary, uint32_t* parts, uint32_t* status,
+                                   hipStream_t stream);
 hipError_t launch_vv_max(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_vv_min(uint64_t* dst, const uint64_t* src, size_t n, hipStream_t stream);
 hipError_t launch_tomb_gc(const TombView& tb, uint32_t n_docs, uint32_t R, const uint64_t* stable, const TombOut& out,
@@ -235,6 +245,7 @@ struct crdt_ctx {
     bool join_stage_stores = true;            // crdt_ctx_set_option("join_stage_stores")
     uint32_t join_slab_per_cu = 0;            // crdt_ctx_set_option("join_slab_blocks_per_cu"): 0 = blocks in order
     bool fold_lean_first = true;              // crdt_ctx_set_option("fold_lean_first")
+    bool digest_tree_fuse = true;             // crdt_ctx_set_option("digest_tree_fuse")
     uint32_t probe_blocks_per_cu = 16;        // crdt_ctx_set_option("probe_blocks_per_cu")
     bool probe_slab = false;                  // crdt_ctx_set_option("probe_slab")
     bool pack_outputs = false;                // crdt_ctx_set_option("pack_batch_outputs")
@@ -587,6 +598,10 @@ int crdt_ctx_set_option(crdt_ctx* ctx, const char* name, int64_t value) {
         ctx->fold_lean_first = value != 0;
         return CRDT_OK;
     }
+    if (!strcmp(name, "digest_tree_fuse")) {  // 0: one launch per level up to the root (digest_tree.hip)
+        ctx->digest_tree_fuse = value != 0;
+        return CRDT_OK;
+    }
     if (!strcmp(name, "join_nt_stores")) {
         ctx->join_nt_stores = value != 0;
         return CRDT_OK;
@@ -805,6 +820,44 @@ int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* 
     return c.end(launch_digest_diff(mine, theirs, n_docs, mask,
                                     CompareOutView{out->flags, out->summary, out->worklist, out->n_work},
                                     ctx->defer.as<uint32_t>(), make_work(ctx).gate, (uint32_t)ctx->n_cu, c.s));
+}
+
+// Digest tree (digest_tree.hip).  The build and the children gather use no
+// workspace.  The diff's partial sums, three words per 64 listed parents, live in
+// the defer buffer: at most n_docs words for the parents of a level of n_docs
+// children, which is what crdt_ctx_reserve(max_docs, ..) sizes it for.
+int crdt_digest_tree_async(crdt_ctx* ctx, const uint64_t* digest, uint32_t n_docs, uint64_t* tree, void* stream) {
+    if (!ctx || check_digest_tree(digest, n_docs, tree) != CRDT_OK) return CRDT_E_INVALID;
+    if (n_docs == 0) return CRDT_OK;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest_tree(digest, n_docs, tree, ctx->digest_tree_fuse, c.s));
+}
+
+int crdt_digest_tree_children_async(crdt_ctx* ctx, const uint64_t* level, uint32_t n_level, const uint32_t* parents,
+                                    const uint32_t* n_parents, uint32_t n_max, uint64_t* out, void* stream) {
+    if (!ctx || check_digest_tree_children(level, n_level, parents, n_parents, n_max, out) != CRDT_OK)
+        return CRDT_E_INVALID;
+    if (n_max == 0) return CRDT_OK;
+    Call c(ctx, stream);
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest_tree_children(level, n_level, parents, n_parents, n_max, out, make_work(ctx).status,
+                                             c.s));
+}
+
+int crdt_digest_tree_diff_async(crdt_ctx* ctx, const uint64_t* mine_level, uint32_t n_level, const uint64_t* theirs,
+                                const uint32_t* parents, const uint32_t* n_parents, uint32_t n_max, uint32_t leaf,
+                                uint32_t mask, uint32_t* idx_out, uint8_t* flags_out, uint32_t* n_out,
+                                uint32_t out_max, uint32_t* summary, void* stream) {
+    if (!ctx || check_digest_tree_diff(mine_level, n_level, theirs, parents, n_parents, n_max, mask, idx_out,
+                                       flags_out, n_out, summary) != CRDT_OK)
+        return CRDT_E_INVALID;
+    Call c(ctx, stream);
+    c.need(ctx->defer, digest_tree_diff_parts(n_max));
+    if (c.rc != CRDT_OK) return c.rc;
+    return c.end(launch_digest_tree_diff(mine_level, n_level, theirs, parents, n_parents, n_max, leaf, mask, idx_out,
+                                         flags_out, n_out, out_max, summary, ctx->defer.as<uint32_t>(),
+                                         make_work(ctx).status, c.s));
 }
 
 // Sub-batch selection / compaction (compare.hip): no workspace.

@@ -443,6 +443,56 @@ inline int check_digest_idx(const crdt_awset_batch* state, const crdt_tomb_batch
     return CRDT_OK;
 }
 
+// ---- digest trees ----------------------------------------------------------------
+
+// The build: both arrays unless there are no documents, the tree off the digest array.
+inline int check_digest_tree(const uint64_t* digest, uint32_t n_docs, const uint64_t* tree) {
+    if (n_docs == 0) return CRDT_OK;
+    if (!digest || !tree || tree == digest) return CRDT_E_INVALID;
+    return CRDT_OK;
+}
+
+// The list of a children / diff call against its level: the identity form
+// (parents == NULL) names parents 0 .. n_max - 1, all of which must be nodes.
+inline bool digest_tree_list_ok(const uint64_t* level, uint32_t n_level, const uint32_t* parents, uint32_t n_max) {
+    if (n_level && !level) return false;
+    const uint64_t n_nodes = ((uint64_t)n_level + CRDT_DIGEST_TREE_FANOUT - 1) / CRDT_DIGEST_TREE_FANOUT;
+    return parents || n_max <= n_nodes;
+}
+
+inline int check_digest_tree_children(const uint64_t* level, uint32_t n_level, const uint32_t* parents,
+                                      const uint32_t* n_parents, uint32_t n_max, const uint64_t* out) {
+    if (!out || !digest_tree_list_ok(level, n_level, parents, n_max)) return CRDT_E_INVALID;
+    Arrays w, in;
+    w.add(out, 8);
+    in.add(level, 8);
+    in.add(parents, 4);
+    in.add(n_parents, 4);
+    if (!off_inputs(w, in, true)) return CRDT_E_INVALID;
+    return CRDT_OK;
+}
+
+// (flags_out and summary are optional)
+inline int check_digest_tree_diff(const uint64_t* mine_level, uint32_t n_level, const uint64_t* theirs,
+                                  const uint32_t* parents, const uint32_t* n_parents, uint32_t n_max, uint32_t mask,
+                                  const uint32_t* idx_out, const uint8_t* flags_out, const uint32_t* n_out,
+                                  const uint32_t* summary) {
+    if (!idx_out || !n_out || (n_max && !theirs) || !digest_tree_list_ok(mine_level, n_level, parents, n_max))
+        return CRDT_E_INVALID;
+    if (mask == 0 || mask > 3u) return CRDT_E_INVALID;
+    Arrays w, in;
+    w.add(idx_out, 4);
+    w.add(flags_out, 1);
+    w.add(n_out, 4, 4);
+    w.add(summary, 4, 5 * 4);
+    in.add(mine_level, 8);
+    in.add(theirs, 8);
+    in.add(parents, 4);
+    in.add(n_parents, 4);
+    if (!starts_distinct(w) || !sized_disjoint(w) || !off_inputs(w, in, true)) return CRDT_E_INVALID;
+    return CRDT_OK;
+}
+
 inline int check_compare(const crdt_awset_batch* a, const crdt_awset_batch* b, uint32_t mask,
                          const crdt_compare_out* out) {
     if (!batch_ptrs_ok(a) || !batch_ptrs_ok(b) || !compare_out_ok(out, mask)) return CRDT_E_INVALID;

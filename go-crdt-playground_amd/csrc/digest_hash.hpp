@@ -47,4 +47,35 @@ CRDT_DIG_FN uint64_t dig_clock(uint32_t r, uint64_t v) {
     return v == 0 ? 0 : dig_fmix(v + kDigV * ((uint64_t)r + 1));
 }
 
+// ---- the digest tree (include/crdtgpu.h, "digest trees") ------------------------
+// A hash tree of fan-out 16 over a digest array; level 0 is the array itself.
+// Word 0 and word 1 are hashed separately all the way up.
+
+constexpr uint32_t kDigTreeFanout = 16;            // CRDT_DIGEST_TREE_FANOUT
+constexpr uint32_t kDigTreeMaxLevels = 8;          // L <= 8 for n_docs < 2^32
+constexpr uint64_t kDigP = 0x2545F4914F6CDD1Dull;  // child slots
+
+// One word of child slot j (0 ... 15) of a node: the term of that node's word.
+CRDT_DIG_FN uint64_t dig_tree_term(uint64_t w, uint32_t j) { return dig_fmix(w + kDigP * ((uint64_t)j + 1)); }
+
+// One word of a node with c children whose terms sum to `sum`.
+CRDT_DIG_FN uint64_t dig_tree_node(uint64_t sum, uint32_t c) { return dig_fmix(sum + kDigN * c); }
+
+// nodes[l] / off[l] for l = 0 ... 8: the nodes of level l (nodes[0] = n_docs) and
+// the node offset of level l >= 1 in the tree array; zero above L, which is returned.
+inline int dig_tree_layout(uint32_t n_docs, uint32_t nodes[9], uint32_t off[9]) {
+    for (int l = 0; l < 9; ++l) nodes[l] = off[l] = 0;
+    nodes[0] = n_docs;
+    if (n_docs == 0) return 0;
+    int l = 0;
+    uint32_t o = 0;
+    do {
+        ++l;
+        nodes[l] = (uint32_t)(((uint64_t)nodes[l - 1] + kDigTreeFanout - 1) / kDigTreeFanout);
+        off[l] = o;
+        o += nodes[l];
+    } while (nodes[l] != 1);
+    return l;
+}
+
 }  // namespace crdt

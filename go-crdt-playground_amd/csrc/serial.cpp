@@ -12,8 +12,12 @@
 //                       the per-document state digest of a host batch: the C
 //                       statement of the definition the kernels (digest.hip)
 //                       compute, for a peer that holds host maps
+//   crdt_digest_tree_layout / crdt_digest_tree_host
+//                       the digest tree over a host digest array, the C statement
+//                       of what digest_tree.hip builds
 //
 // Host buffers only; no GPU.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -334,6 +338,43 @@ int crdt_awset_digest_host(const crdt_awset_batch* state, const crdt_tomb_batch*
         for (uint32_t r = 0; r < R; ++r) w1 += dig_clock(r, state->vv[(size_t)d * R + r]);
         digest[2 * (size_t)d] = dig_fmix(w0 + kDigN * n);
         digest[2 * (size_t)d + 1] = dig_fmix(w1 + kDigN * (n + m));
+    }
+    return CRDT_OK;
+}
+
+int crdt_digest_tree_layout(uint32_t n_docs, uint32_t level_nodes[9], uint32_t level_off[9]) {
+    uint32_t nodes[9], off[9];
+    const int L = crdt::dig_tree_layout(n_docs, nodes, off);
+    for (int l = 0; l < 9; ++l) {
+        if (level_nodes) level_nodes[l] = nodes[l];
+        if (level_off) level_off[l] = off[l];
+    }
+    return L;
+}
+
+// The definition of the digest tree (include/crdtgpu.h), level by level, node by
+// node, child by child.
+int crdt_digest_tree_host(const uint64_t* digest, uint32_t n_docs, uint64_t* tree) {
+    using namespace crdt;
+    if (n_docs == 0) return CRDT_OK;
+    if (!digest || !tree) return CRDT_E_INVALID;
+    uint32_t nodes[9], off[9];
+    const int L = dig_tree_layout(n_docs, nodes, off);
+    const uint64_t* child = digest;
+    for (int l = 1; l <= L; ++l) {
+        uint64_t* node = tree + 2 * (size_t)off[l];
+        for (uint32_t i = 0; i < nodes[l]; ++i) {
+            const uint64_t first = (uint64_t)i * kDigTreeFanout;
+            const uint32_t c = (uint32_t)std::min<uint64_t>(kDigTreeFanout, nodes[l - 1] - first);
+            uint64_t s0 = 0, s1 = 0;
+            for (uint32_t j = 0; j < c; ++j) {
+                s0 += dig_tree_term(child[2 * (first + j)], j);
+                s1 += dig_tree_term(child[2 * (first + j) + 1], j);
+            }
+            node[2 * (size_t)i] = dig_tree_node(s0, c);
+            node[2 * (size_t)i + 1] = dig_tree_node(s1, c);
+        }
+        child = node;
     }
     return CRDT_OK;
 }

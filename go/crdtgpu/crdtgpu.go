@@ -1115,6 +1115,110 @@ func (e *Engine) DigestIdx(state *C.crdt_awset_batch, tombs *C.crdt_tomb_batch, 
 	return nil
 }
 
+// DigestTreeFanout is the fan-out of the digest tree: one node covers 16 children.
+const DigestTreeFanout = uint32(C.CRDT_DIGEST_TREE_FANOUT)
+
+// DigestTreeLayout is the shape of the digest tree over nDocs documents
+// (crdt_digest_tree_layout): L levels above the digest array, Nodes[l] nodes on
+// level l (Nodes[0] = nDocs) and Off[l] the node offset of level l >= 1 in the
+// tree array, which holds two words per node.
+type DigestTreeLayout struct {
+	L     int
+	Nodes [9]uint32
+	Off   [9]uint32
+}
+
+// TreeLayout computes the layout on the host.
+func TreeLayout(nDocs uint32) DigestTreeLayout {
+	var t DigestTreeLayout
+	var nodes, off [9]C.uint32_t
+	t.L = int(C.crdt_digest_tree_layout(C.uint32_t(nDocs), &nodes[0], &off[0]))
+	for l := range nodes {
+		t.Nodes[l], t.Off[l] = uint32(nodes[l]), uint32(off[l])
+	}
+	return t
+}
+
+// TreeWords is the length of the tree array in uint64 words.
+func (t DigestTreeLayout) TreeWords() int {
+	if t.L == 0 {
+		return 0
+	}
+	return 2 * (int(t.Off[t.L]) + 1)
+}
+
+// DigestTreeHost builds the digest tree of a host digest array (two words per
+// document, as Digest returns them flattened) without a GPU
+// (crdt_digest_tree_host): levels 1 .. L concatenated, two words per node.
+func DigestTreeHost(digest []uint64) ([]uint64, error) {
+	n := uint32(len(digest) / 2)
+	tree := make([]uint64, TreeLayout(n).TreeWords()+2)
+	if n == 0 {
+		return tree[:0], nil
+	}
+	if rc := C.crdt_digest_tree_host(p64(digest), C.uint32_t(n), p64(tree)); rc != 0 {
+		return nil, errOf("crdt_digest_tree_host", rc)
+	}
+	return tree[:len(tree)-2], nil
+}
+
+// DigestTree builds every level of the tree over a device digest array
+// (crdt_digest_tree_async). digest and tree are device pointers; the tree is
+// rebuilt whole from the array, which DigestIdx keeps current. Asynchronous on
+// stream.
+func (e *Engine) DigestTree(digest *C.uint64_t, nDocs uint32, tree *C.uint64_t, stream unsafe.Pointer) error {
+	if rc := C.crdt_digest_tree_async(e.ctx, digest, C.uint32_t(nDocs), tree, stream); rc != 0 {
+		return errOf("crdt_digest_tree_async", rc)
+	}
+	return nil
+}
+
+// DigestTreeChildren is the sender's side of a descent
+// (crdt_digest_tree_children_async): both words of the 16 children of every
+// listed parent packed into out, 32 words per parent, zeros past the level.
+// level is the node array the children lie in (the digest array, or the tree at
+// 2*Off[l-1]) and nLevel its node count. parents and nParents are device
+// pointers; parents nil is the identity, nParents nil means nMax. Asynchronous
+// on stream; device-side errors surface at the context's next sync.
+func (e *Engine) DigestTreeChildren(level *C.uint64_t, nLevel uint32, parents, nParents *C.uint32_t, nMax uint32,
+	out *C.uint64_t, stream unsafe.Pointer) error {
+	if out == nil {
+		return fmt.Errorf("DigestTreeChildren: nil argument")
+	}
+	if rc := C.crdt_digest_tree_children_async(e.ctx, level, C.uint32_t(nLevel), parents, nParents, C.uint32_t(nMax),
+		out, stream); rc != 0 {
+		return errOf("crdt_digest_tree_children_async", rc)
+	}
+	return nil
+}
+
+// DigestTreeDiff is the receiver's side (crdt_digest_tree_diff_async): the
+// listed parents' children of its own level against theirs, the peer's packed
+// children for the same list. The children with flag & mask go to idxOut,
+// ascending, their flags to flagsOut (may be nil) and their exact number to
+// nOut; summary (may be nil) gets five counts. leaf: the children are documents
+// and the flags are those of the digest comparison; otherwise bit 0 is "word 0
+// differs" and bit 1 "word 1 differs". idxOut and nOut are the parents and
+// nParents of the next level's two calls. All pointers are device pointers.
+// Asynchronous on stream; device-side errors surface at the context's next sync.
+func (e *Engine) DigestTreeDiff(mineLevel *C.uint64_t, nLevel uint32, theirs *C.uint64_t, parents, nParents *C.uint32_t,
+	nMax uint32, leaf bool, mask uint32, idxOut *C.uint32_t, flagsOut *C.uint8_t, nOut *C.uint32_t, outMax uint32,
+	summary *C.uint32_t, stream unsafe.Pointer) error {
+	if idxOut == nil || nOut == nil {
+		return fmt.Errorf("DigestTreeDiff: nil argument")
+	}
+	isLeaf := C.uint32_t(0)
+	if leaf {
+		isLeaf = 1
+	}
+	if rc := C.crdt_digest_tree_diff_async(e.ctx, mineLevel, C.uint32_t(nLevel), theirs, parents, nParents,
+		C.uint32_t(nMax), isLeaf, C.uint32_t(mask), idxOut, flagsOut, nOut, C.uint32_t(outMax), summary,
+		stream); rc != 0 {
+		return errOf("crdt_digest_tree_diff_async", rc)
+	}
+	return nil
+}
+
 // ---------------------------------------------------------------- merge diff
 
 // DocDiff is what turns one document's `before` into its `after`: merge's

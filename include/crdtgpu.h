@@ -41,6 +41,11 @@
  *   crdt_awset_digest_idx_async
  *       the digests of the documents a worklist names, written into a
  *       resident digest array at their own positions (no reference counterpart)
+ *   crdt_digest_tree_async / crdt_digest_tree_host / crdt_digest_tree_children_async /
+ *   crdt_digest_tree_diff_async
+ *       a hash tree over a digest array and the two sides of a level-by-level
+ *       descent: which documents differ, from a few kilobytes instead of the
+ *       whole array (no reference counterpart)
  *   crdt_awset_select_async
  *       those documents (or all of them: compaction) gathered into a packed
  *       batch for the next round (no reference counterpart)
@@ -223,6 +228,8 @@ int crdt_ctx_set_max_doc_entries(crdt_ctx* ctx, uint32_t max_entries);
  *   "join_slab_blocks_per_cu" 0..64   wave kernel block order: slabs of G = this x CUs
  *                                     blocks (crdt_device.hpp SlabMap; 0 = in order)
  *   "fold_lean_first"     0|1         folds: slot-walk pass first, the rest deferred (default 1)
+ *   "digest_tree_fuse"    0|1         digest tree: the levels of 4,096 children and fewer in
+ *                                     one workgroup's launch (default 1)
  *   "join_tile_capacity"  1..2^28     large documents: merge-path tiles of 1,024 merged
  *                                     positions per pass (default 2^22, 56 B each,
  *                                     allocated on first use); a call with more tiles runs
@@ -651,6 +658,117 @@ int crdt_digest_diff_async(crdt_ctx* ctx, const uint64_t* mine, const uint64_t* 
 int crdt_awset_digest_idx_async(crdt_ctx* ctx, const crdt_awset_batch* state, const crdt_tomb_batch* tombs /* or NULL */,
                                 const uint32_t* idx, const uint32_t* n_idx /* or NULL */, uint32_t n_max,
                                 uint32_t n_digest_docs, uint32_t mode, uint64_t* digest, void* stream);
+
+/* ---- digest trees: find differing documents without shipping every digest ----
+ * crdt_digest_diff_async needs the peer's whole digest array, 16 B a document,
+ * also when nothing differs.  A hash tree of fixed fan-out over the array lets
+ * two peers find the differing documents level by level: the receiver names the
+ * nodes that differ, the sender packs their children (256 B a node), the
+ * receiver diffs them against its own and names the next level.  At level 0 the
+ * list is the document worklist, with the flags of crdt_digest_diff_async; it
+ * feeds crdt_awset_select_async, crdt_replica_select_async and
+ * crdt_awset_digest_idx_async as it stands.
+ * The definition is part of the ABI and does not change (fmix, K_N: above):
+ *   CRDT_DIGEST_TREE_FANOUT = 16      K_P = 0x2545F4914F6CDD1D
+ *   Level 0 is the caller's digest array, n_0 = n_docs nodes of two words; it is
+ *   not copied into the tree.  Level l >= 1 has n_l = ceil(n_(l-1) / 16) nodes.
+ *   L is the smallest l >= 1 with n_l == 1: one document still has a root above
+ *   it, n_docs == 0 has no levels, L <= 8.
+ *   tree is [2 * sum_(l=1..L) n_l] u64: the levels concatenated from level 1
+ *   upwards, level l starting at node offset sum_(1<=k<l) n_k.
+ *   Node i of level l has the c children 16i .. min(16i + 15, n_(l-1) - 1) of
+ *   level l-1.  For each word w of 0 and 1 separately:
+ *     node[w] = fmix( sum_(j<c) fmix(child_j[w] + K_P*(j+1)) + K_N*c )   mod 2^64
+ *   - The slot salt K_P*(j+1) makes two swapped children show.
+ *   - The sum keeps the value independent of how the work is cut up: the tree is
+ *     bit-identical on every run, on the device and on the host.
+ *   - The words stay separate: word 0 of a node covers exactly the element sets
+ *     below it, word 1 everything else (dots, tombstones, clocks), so the
+ *     ELEMENTS / STATE distinction carries up the tree.
+ * There is no incremental update, deliberately: rebuilding reads the digest
+ * array once (16 MB + 1 MB at 2^20 documents), while re-deriving the ancestors of
+ * a k-document worklist reads 256 B * L per document before de-duplication and
+ * touches nearly every level-1 node from about 5 % random documents on.  Keep
+ * the array current with crdt_awset_digest_idx_async, then rebuild the tree whole.
+ *
+ * crdt_digest_tree_layout (host): level_nodes[l] = n_l for l = 0 .. L and
+ * level_off[l] = the node offset of level l >= 1 in `tree`, zeros above L;
+ * returns L.  The tree holds level_off[L] + 1 nodes.  Either array may be NULL.
+ * crdt_digest_tree_host: the definition over host arrays, no GPU and no context,
+ * for the peer that holds host maps.  CRDT_E_INVALID: NULL digest or tree with
+ * n_docs > 0.
+ * crdt_digest_tree_async: digest [2*n_docs] and tree on the device; every level
+ * is built, one launch per level and one for all levels of 4,096 children and
+ * fewer.  No workspace, no allocation, no host sync, kernel nodes only,
+ * capturable on an unreserved context; ordered after the context's previous
+ * call like every entry point.  n_docs == 0 launches nothing.  Arrays that are
+ * only 8 B aligned are read and written word by word.  CRDT_E_INVALID: NULL
+ * digest or tree with n_docs > 0, tree starting where digest starts.
+ *
+ * crdt_digest_tree_children_async, the sender's side.  `level` is the node array
+ * of level l-1 with n_level nodes (the digest array, or tree + 2*level_off[l-1]);
+ * `parents` a device list of node indices of level l, in any order, NULL: the
+ * identity j -> j; n_parents one device word, NULL: n_max.  For
+ * j < min(*n_parents, n_max) and c < 16 both words of child 16*parents[j] + c are
+ * written to out[2*(16j + c)], out[2*(16j + c) + 1]; a child at or past n_level
+ * is written as zeros; no word of out past 32 * min(*n_parents, n_max) is
+ * touched.  The identity form is the level itself padded to a multiple of 16,
+ * which is how a descent may start at any level.  Reported by crdt_ctx_sync:
+ *   CRDT_E_CAPACITY  *n_parents > n_max (clamped to n_max)
+ *   CRDT_E_INVALID   parents[j] >= ceil(n_level / 16): that parent's 16 slots are
+ *                    zeros, every other is exact
+ * Returned by the call, CRDT_E_INVALID: NULL out, NULL level with n_level > 0,
+ * out starting where level, parents or n_parents starts, n_max above
+ * ceil(n_level / 16) in the identity form.  No workspace; capturable on an
+ * unreserved context.  n_max == 0 launches nothing.
+ *
+ * crdt_digest_tree_diff_async, the receiver's side.  mine_level / n_level: the
+ * receiver's own level l-1; theirs: the packed array the peer's children call
+ * wrote for the same parents / n_parents / n_max.  For every listed parent and
+ * every child below n_level, e is "word 0 differs" and s "word 1 differs".
+ *   leaf != 0  the children are documents: flag = CRDT_DIG_ELEMENTS if e, else
+ *              CRDT_DIG_STATE if s; a child is listed iff flag & mask, exactly
+ *              crdt_digest_diff_async's rule.
+ *   leaf == 0  the children are nodes: flag = e | (s << 1), not exclusive; a
+ *              child is listed iff flag & mask.  This is a superset: a node whose
+ *              word 0 differs may still hide a document that differs in word 1
+ *              only, so word 1 keeps its own bit.
+ *   idx_out    the listed child indices, ascending (out_max words of room), and
+ *   flags_out  (u8, parallel to it, or NULL) their flags
+ *   n_out      one word: their exact total
+ *   summary    (5 words, or NULL) [0] children with e (leaf: ELEMENTS), [1] with
+ *              s (leaf: STATE), [2] and [3] zero, [4] children listed
+ * Positions come from a count, a scan of the partial sums and an emit: no atomic
+ * decides a position, the result is the same on every run.  idx_out / n_out are
+ * the parents / n_parents of the next level's two calls with no host round trip.
+ * `parents` must be strictly ascending, which a previous level's idx_out is.
+ * Reported by crdt_ctx_sync:
+ *   CRDT_E_CAPACITY  the total is above out_max: *n_out and summary are exact,
+ *                    nothing is written at or past out_max; or *n_parents > n_max
+ *                    (clamped)
+ *   CRDT_E_INVALID   parents not strictly ascending, or a parent that is no node
+ *                    (it lists nothing); every write stays in bounds
+ * Returned by the call, CRDT_E_INVALID: NULL idx_out or n_out, NULL theirs with
+ * n_max > 0, NULL mine_level with n_level > 0, mask outside 1..3, two of the
+ * written arrays starting at one address or one of them where an input starts,
+ * n_max above ceil(n_level / 16) in the identity form.  The partial sums (three
+ * words per 64 listed parents) follow the workspace rules of
+ * crdt_awset_scatter_async: crdt_ctx_reserve(max_docs, ..) covers every level of
+ * max_docs documents, and a call that would have to grow the buffer while its
+ * stream is capturing returns CRDT_E_WORKSPACE.  n_max == 0 still writes *n_out
+ * and the summary. */
+#define CRDT_DIGEST_TREE_FANOUT 16u
+int crdt_digest_tree_layout(uint32_t n_docs, uint32_t level_nodes[9] /* or NULL */, uint32_t level_off[9] /* or NULL */);
+int crdt_digest_tree_host(const uint64_t* digest, uint32_t n_docs, uint64_t* tree);
+int crdt_digest_tree_async(crdt_ctx* ctx, const uint64_t* digest, uint32_t n_docs, uint64_t* tree, void* stream);
+int crdt_digest_tree_children_async(crdt_ctx* ctx, const uint64_t* level, uint32_t n_level,
+                                    const uint32_t* parents /* or NULL */, const uint32_t* n_parents /* or NULL */,
+                                    uint32_t n_max, uint64_t* out, void* stream);
+int crdt_digest_tree_diff_async(crdt_ctx* ctx, const uint64_t* mine_level, uint32_t n_level, const uint64_t* theirs,
+                                const uint32_t* parents /* or NULL */, const uint32_t* n_parents /* or NULL */,
+                                uint32_t n_max, uint32_t leaf, uint32_t mask, uint32_t* idx_out,
+                                uint8_t* flags_out /* or NULL */, uint32_t* n_out, uint32_t out_max,
+                                uint32_t* summary /* or NULL */, void* stream);
 
 /* ---- select: a subset of documents (or all: compaction) as a packed batch --
  * out gets n_out documents packed with no slack: out->offsets[j] is the
